@@ -10,6 +10,10 @@ update and LR-scheduler step -- nothing is skipped.
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 it is launched by
 ``torch.distributed.run`` (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from env).
 Rank 0 prints ONE JSON line; ``value`` is the whole-job aggregate tokens/s (max time over ranks).
+Such a plain run sets up, warms up, times the K steps and prints. ``--full`` adds what the headline
+figure does not need, after the clock stopped: the cross-rank replica checksum (exit code 3 on a
+mismatch) and, for N>1, the all-reduce probe of ``--comm-probe``. ``--dump-outputs DIR`` writes what
+the last timed step computed (loss, updated parameters, AdamW moments) as ``DIR/<name>.npy``.
 
 Started as ``python bench.py --gpus N`` (N>1) WITHOUT a rank environment, this process touches no
 GPU: it starts ``torch.distributed.run`` with N ranks as a child process on 127.0.0.1 and exits
@@ -65,13 +69,44 @@ def parse():
     ap.add_argument("--sparse-embedding-grad", choices=["auto", "on", "off"], default="auto",
                     help="W > 1: token-embedding gradient as (id, row) pairs (auto: tokens per step <= vocab / 2)")
     ap.add_argument("--comm-probe", choices=["rccl", "all", "off"], default="rccl",
-                    help="W > 1, after the timed steps: all-reduce probe bus bandwidth on the job's group "
+                    help="--full, W > 1, after the timed steps: all-reduce probe bus bandwidth on the job's group "
                          "(rccl; all: also the direct xGMI engine) reported in the JSON line")
     ap.add_argument("--cpu", action="store_true",
                     help="run on the CPU over gloo (tests of the launcher and the DDP path; not a benchmark)")
     ap.add_argument("--gemm-tuning", choices=["auto", "off", "tune"], default="auto",
                     help="hipBLASLt solution table (tuning/): auto = use the committed table if present")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and measurements the headline figure does not "
+                         "need: the cross-rank replica checksum (exit code 3 on a mismatch) and, W > 1, --comm-probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned and updated (loss, parameters, "
+                         "AdamW moments; a fixed seeded sample of each large buffer) as DIR/<name>.npy in float32")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of each large buffer (8 MiB as float32)
+
+
+def dump_outputs(path, loss, flat, opt):
+    """Rank 0: the last timed step's results as float32 .npy files. Buffers larger than DUMP_SAMPLE
+    elements are sampled at fixed positions (seeded by the buffer's length alone), so two builds run
+    with the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "params": flat.data, "exp_avg": opt.exp_avg,
+              "exp_avg_sq": opt.exp_avg_sq}
+    if getattr(opt, "master", None) is not None:
+        arrays["master_params"] = opt.master
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def free_port() -> int:
@@ -268,12 +303,16 @@ def main():
         torch.distributed.all_reduce(dt_t, op=torch.distributed.ReduceOp.MAX)
     dt = float(dt_t.item())
     final_loss = float(loss.item())
-    # after the clock stopped: are the replicas still identical? (parallel/consistency.py)
-    from pyrecover_amd.parallel.consistency import replica_report
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, flat, opt)
+    replicas = None
+    if args.full:
+        # after the clock stopped: are the replicas still identical? (parallel/consistency.py)
+        from pyrecover_amd.parallel.consistency import replica_report
 
-    replicas = replica_report(flat, opt)
+        replicas = replica_report(flat, opt)
     probe = None
-    if world > 1 and args.comm_probe != "off":
+    if args.full and world > 1 and args.comm_probe != "off":
         # after the clock stopped: the group's all-reduce latency / bus bandwidth, measured
         from pyrecover_amd.parallel import bucket_tune as BT
 
@@ -335,15 +374,18 @@ def main():
             "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1) if dev.type == "cuda" else None,
             "gemm_table": bool(torch.cuda.tunable.is_enabled()) if dev.type == "cuda" else False,
             "hip_graph": bool(args.graph),
-            "params_identical_across_ranks": replicas["params_identical_across_ranks"],
-            "optimizer_identical_across_ranks": replicas["optimizer_identical_across_ranks"],
+            "full": bool(args.full),
         }
-        if replicas["mismatched"]:
-            out["replica_checksums"] = {k: replicas["checksums"][k] for k in replicas["mismatched"]}
+        if replicas is not None:
+            out["params_identical_across_ranks"] = replicas["params_identical_across_ranks"]
+            out["optimizer_identical_across_ranks"] = replicas["optimizer_identical_across_ranks"]
+            if replicas["mismatched"]:
+                out["replica_checksums"] = {k: replicas["checksums"][k] for k in replicas["mismatched"]}
         if world > 1:
             out["comm"] = comm
             out["comm_env"] = comm_env()
-            out["comm_probe"] = probe
+            if args.full:
+                out["comm_probe"] = probe
         if phases:
             n = len(phases)
             out["phase_ms"] = {k: round(sum(e[i].elapsed_time(e[i + 1]) for e in phases) / n, 2)
@@ -355,7 +397,7 @@ def main():
         flush_tuning()
     if world > 1:
         torch.distributed.destroy_process_group()
-    if replicas["mismatched"]:
+    if replicas is not None and replicas["mismatched"]:
         print(f"error: replicas differ across ranks after the timed steps: {replicas['mismatched']}", file=sys.stderr)
         sys.exit(3)
 

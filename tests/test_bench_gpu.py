@@ -50,7 +50,7 @@ def test_bench_gpus2_sharded_optimizer_sparse_embedding_replicas_identical(cuda)
     for extra in ([], ["--shard-optimizer", "--sparse-embedding-grad", "on"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "gpt2-small",
                             "--batch-per-gpu", "2", "--steps", "3", "--warmup", "1", "--bucket-mb", "32",
-                            "--sparse-embedding-grad", "off"] + extra,
+                            "--sparse-embedding-grad", "off", "--full"] + extra,
                            capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
         assert r.returncode == 0, (r.stdout + r.stderr)[-5000:]
         line = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1]
@@ -70,7 +70,7 @@ def test_bench_gpus2_auto_shards_a_gqa_batch1_job(cuda):
     env.update(PYRECOVER_LOCAL_DEVICE="0", PYRECOVER_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--model", "llama-tiny",
                         "--batch-per-gpu", "1", "--seq-len", "256", "--steps", "3", "--warmup", "1",
-                        "--bucket-mb", "0.25"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+                        "--bucket-mb", "0.25", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-5000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
     assert out["config"]["shard_optimizer"] is True and not out["config"]["weight_shadows"]

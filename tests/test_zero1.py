@@ -234,7 +234,7 @@ def test_bench_cpu_two_ranks_reports_identical_replicas():
     env = dict(os.environ, PYRECOVER_DIST_BACKEND="gloo", OMP_NUM_THREADS="2")
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--cpu", "--model", "llama-micro", "--steps", "2",
            "--warmup", "1", "--batch-per-gpu", "2", "--seq-len", "64", "--bucket-mb", "0.05", "--shard-optimizer",
-           "--sparse-embedding-grad", "on"]
+           "--sparse-embedding-grad", "on", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
