@@ -187,8 +187,9 @@ at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& h, const at::Te
 }
 
 // In-place RoPE on the first `ncols` columns of each row of a 2-D [tokens, ld] buffer.
+// doc_start (optional, int32 [B, S] with B * S = tokens): packed sequences, positions restart per document.
 void rope_(at::Tensor x2d, int64_t ncols, const at::Tensor& tab, int64_t head_dim, int64_t seq_len,
-           int64_t pos_offset, bool inverse) {
+           int64_t pos_offset, bool inverse, const c10::optional<at::Tensor>& doc_start) {
   const Range range_("pyrecover::rope");
   check_dev(x2d, "x");
   check_row_major(x2d, "rope x");
@@ -197,9 +198,17 @@ void rope_(at::Tensor x2d, int64_t ncols, const at::Tensor& tab, int64_t head_di
   TORCH_CHECK(tab.numel() >= (seq_len + pos_offset) * head_dim, "rope: table too small");
   TORCH_CHECK(ncols <= x2d.size(1) && ncols % head_dim == 0 && head_dim % 8 == 0, "rope: bad ncols/head_dim");
   TORCH_CHECK(x2d.size(0) % seq_len == 0, "rope: tokens must be a multiple of seq_len");
+  const int* ds = nullptr;
+  if (doc_start.has_value()) {
+    TORCH_CHECK(doc_start->scalar_type() == at::kInt && doc_start->is_contiguous() &&
+                    doc_start->numel() == x2d.size(0) && doc_start->size(-1) == seq_len,
+                "rope: doc_start must be contiguous int32 [tokens / seq_len, seq_len]");
+    same_dev(x2d, *doc_start, "doc_start");
+    ds = doc_start->data_ptr<int>();
+  }
   const c10::DeviceGuard guard(x2d.device());
   check(pra_rope(dt(x2d), x2d.data_ptr(), tab.data_ptr(), x2d.size(0), (int)x2d.stride(0), (int)ncols, (int)head_dim,
-                 (int)seq_len, (int)pos_offset, inverse ? 1 : 0, stream_of(x2d)),
+                 (int)seq_len, (int)pos_offset, inverse ? 1 : 0, ds, stream_of(x2d)),
         "rope");
 }
 
@@ -693,8 +702,28 @@ at::Tensor pad_seq(const at::Tensor& t, int64_t Sp) {
   return out;
 }
 
+// doc_start [B, S] int32 of a packed batch (attention_docs.hip): checked, and for a sequence that does not
+// tile, padded to Sp with the last document's start, so pad tokens continue the last document
+// (device ops only: the step may be under graph capture).
+void check_doc_start(const at::Tensor& q, const at::Tensor& ds, int64_t B, int64_t S, bool causal) {
+  TORCH_CHECK(causal, "attention: doc_start implies causal attention");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf,
+              "attention: the document-masked kernels take bf16 or fp16 (fp32 / fp64 run torch math in "
+              "pyrecover_amd.ops.fused)");
+  TORCH_CHECK(ds.scalar_type() == at::kInt && ds.dim() == 2 && ds.size(0) == B && ds.size(1) == S &&
+                  ds.is_contiguous(), "attention: doc_start must be contiguous int32 [B, S]");
+  same_dev(q, ds, "doc_start");
+}
+at::Tensor pad_doc_start(const at::Tensor& ds, int64_t Sp) {
+  const int64_t B = ds.size(0), S = ds.size(1);
+  at::Tensor out = at::empty({B, Sp}, ds.options());
+  out.narrow(1, 0, S).copy_(ds);
+  out.narrow(1, S, Sp - S).copy_(ds.narrow(1, S - 1, 1).expand({B, Sp - S}));
+  return out;
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
-                                 bool causal) {
+                                 bool causal, const c10::optional<at::Tensor>& doc_start) {
   const Range range_("pyrecover::attn_fwd");
   check_dev(q, "q");
   check_attn_dtype(q);
@@ -708,6 +737,21 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
   TORCH_CHECK(Hq % Hkv == 0, "attention: n_heads must be a multiple of n_kv_heads");
   TORCH_CHECK(S > 0 && (S % 64 == 0 || S <= (int64_t)INT32_MAX - kSeqPad), "attention: bad seq_len");
   const c10::DeviceGuard guard(q.device());
+  if (doc_start.has_value()) {  // packed sequences: document-masked kernels (128-row blocks)
+    check_doc_start(q, *doc_start, B, S, causal);
+    const bool pad = S % kSeqPad != 0;
+    const int64_t Sp = round_up(S, kSeqPad);
+    at::Tensor qp = pad ? pad_seq(q, Sp) : q, kp = pad ? pad_seq(k, Sp) : k, vp = pad ? pad_seq(v, Sp) : v;
+    at::Tensor dsp = pad ? pad_doc_start(*doc_start, Sp) : *doc_start;
+    at::Tensor o = at::empty({B, Sp, Hq, D}, q.options());
+    at::Tensor lse = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+    check(pra_attn_docs_fwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                            dsp.data_ptr<int>(), (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D, qp.stride(1),
+                            kp.stride(1), vp.stride(1), o.stride(1), (float)scale, stream_of(q)),
+          "attn_docs_fwd");
+    if (pad) return {o.narrow(1, 0, S).contiguous(), lse.narrow(2, 0, S).contiguous()};
+    return {o, lse};
+  }
   const int64_t fwd_tile = q.scalar_type() == at::kFloat ? 128 : 64;  // fp32 kernel: 128-query blocks
   if (S % fwd_tile) {
     const int64_t Sp = round_up(S, kSeqPad);
@@ -732,7 +776,8 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
 // Writes dq/dk/dv into caller-provided [B,S,H,D] views (e.g. slices of a fused dQKV buffer).
 void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& dout, const at::Tensor& lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
-              bool causal, c10::optional<at::Tensor> rope_tab, int64_t mid_event) {
+              bool causal, c10::optional<at::Tensor> rope_tab, int64_t mid_event,
+              const c10::optional<at::Tensor>& doc_start) {
   const Range range_("pyrecover::attn_bwd");
   // mid_event (optional, a torch.cuda.Event's cuda_event handle): recorded on the stream between the
   // dQ and dK/dV kernels, so another stream can start work under the dK/dV kernel
@@ -764,6 +809,33 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
     rtab = tb.data_ptr<float>();
   }
   const c10::DeviceGuard guard(q.device());
+  if (doc_start.has_value()) {  // packed sequences: document-masked kernels
+    check_doc_start(q, *doc_start, B, S, causal);
+    const bool pad = S % kSeqPad != 0;
+    const int64_t Sp = round_up(S, kSeqPad);
+    at::Tensor qp = q, kp = k, vp = v, op = o, dop = dout, lp = lse, dqp = dq, dkp = dk, dvp = dv, dsp = *doc_start;
+    if (pad) {
+      qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp), op = pad_seq(o, Sp), dop = pad_seq(dout, Sp);
+      lp = at::zeros({B, Hq, Sp}, lse.options());  // padded rows: any finite lse (their dO is zero)
+      lp.narrow(2, 0, S).copy_(lse.view({B, Hq, S}));
+      dqp = at::empty_like(qp), dkp = at::empty_like(kp), dvp = at::empty_like(vp);
+      dsp = pad_doc_start(*doc_start, Sp);
+    }
+    at::Tensor ws = at::empty({pra_attn_docs_bwd_workspace((int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D)},
+                              q.options().dtype(at::kFloat));
+    check(pra_attn_docs_bwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(),
+                            lp.data_ptr<float>(), ws.data_ptr<float>(), dqp.data_ptr(), dkp.data_ptr(),
+                            dvp.data_ptr(), dsp.data_ptr<int>(), (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D,
+                            qp.stride(1), kp.stride(1), vp.stride(1), op.stride(1), dop.stride(1), dqp.stride(1),
+                            dkp.stride(1), dvp.stride(1), (float)scale, (int)S, rtab, mev, stream_of(q)),
+          "attn_docs_bwd");
+    if (pad) {
+      dq.copy_(dqp.narrow(1, 0, S));
+      dk.copy_(dkp.narrow(1, 0, S));
+      dv.copy_(dvp.narrow(1, 0, S));
+    }
+    return;
+  }
   if (S % kSeqPad) {
     const int64_t Sp = round_up(S, kSeqPad);
     at::Tensor qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp), op = pad_seq(o, Sp),
@@ -808,7 +880,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
-  m.def("rope_", &rope_);
+  m.def("rope_", &rope_, pybind11::arg("x2d"), pybind11::arg("ncols"), pybind11::arg("tab"),
+        pybind11::arg("head_dim"), pybind11::arg("seq_len"), pybind11::arg("pos_offset"), pybind11::arg("inverse"),
+        pybind11::arg("doc_start") = pybind11::none());
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd, pybind11::arg("dy"), pybind11::arg("gu"), pybind11::arg("out") = pybind11::none(),
         pybind11::arg("variant") = -1);
@@ -840,11 +914,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("swiglu_bwd_t_", &swiglu_bwd_t_);
   m.def("swiglu_fwd_t", &swiglu_fwd_t);
   m.def("rope_t_", &rope_t_);
-  m.def("attn_fwd", &attn_fwd);
+  m.def("attn_fwd", &attn_fwd, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("scale"),
+        pybind11::arg("causal"), pybind11::arg("doc_start") = pybind11::none());
   m.def("attn_bwd", &attn_bwd, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"),
         pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("dq"), pybind11::arg("dk"), pybind11::arg("dv"),
         pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("rope_tab") = pybind11::none(),
-        pybind11::arg("mid_event") = 0);
+        pybind11::arg("mid_event") = 0, pybind11::arg("doc_start") = pybind11::none());
   m.def("attn_set_order", [](int fwd, int dq, int dkdv) { pra_attn_set_order(fwd, dq, dkdv); },
         "block order of the attention grids: 0 = heavy tiles first, G > 0 = XCD-grouped with G heads per group, "
         "-1 = by shape", pybind11::arg("fwd"), pybind11::arg("dq"), pybind11::arg("dkdv"));

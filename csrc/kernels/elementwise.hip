@@ -23,6 +23,8 @@ static inline int grid_for(size_t work_items, int block = 256) {
 // x points at the first rotated column of token 0; `ld` is the token row stride; the first
 // `ncols` columns of each row (q heads followed by k heads, head_dim D each) are rotated.
 // tab is float2[S][D/2] = (cos, sin). sign = -1 applies the inverse rotation (backward).
+// doc_start (optional, int32 per token: packed sequences): the position of token t restarts at its
+// document, (t % S) - doc_start[t], with doc_start clamped into [0, t % S] (a row of the table).
 // (a + ib) * (c + is) with the FMA placement spelled out, so every RoPE kernel (row-major,
 // transposing, register-tile) rounds identically whatever the compiler's contraction choices.
 __device__ __forceinline__ void rot_pair(float a, float b, float c, float s, float& o0, float& o1) {
@@ -33,13 +35,16 @@ __device__ __forceinline__ void rot_pair(float a, float b, float c, float s, flo
 template <typename T>
 __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ x, const float2* __restrict__ tab,
                                                    long ntok, int ld, int ncols, int D, int S,
-                                                   int pos_offset, float sign) {
+                                                   int pos_offset, float sign,
+                                                   const int* __restrict__ doc_start) {
   const int vpr = ncols / 8;  // 8-element vectors per row
   const long total = ntok * vpr;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const long t = idx / vpr;
     const int col = (int)(idx - t * vpr) * 8;
-    const int pos = (int)(t % S) + pos_offset;
+    int pos = (int)(t % S);
+    if (doc_start != nullptr) pos -= min(max(doc_start[t], 0), pos);
+    pos += pos_offset;
     const int pi = (col % D) / 2;  // first pair index
     T* p = x + t * (long)ld + col;
     float v[8];
@@ -429,13 +434,13 @@ __global__ __launch_bounds__(256) void rope_t_reg_kernel(T* x, T* __restrict__ x
 extern "C" {
 
 hipError_t pra_rope(int dtype, void* x, const void* tab, long ntok, int ld, int ncols, int D, int S,
-                    int pos_offset, int inverse, hipStream_t s) {
+                    int pos_offset, int inverse, const int* doc_start, hipStream_t s) {
   if (ncols % 8 || D % 8 || ld % 8) return hipErrorInvalidValue;
   const int grid = pra::grid_for((size_t)ntok * (ncols / 8));
   PRA_DISPATCH_FLOAT(dtype, T,
                      hipLaunchKernelGGL((pra::rope_kernel<T>), dim3(grid), dim3(256), 0, s, (T*)x,
                                         (const float2*)tab, ntok, ld, ncols, D, S, pos_offset,
-                                        inverse ? -1.f : 1.f));
+                                        inverse ? -1.f : 1.f, doc_start));
   return hipGetLastError();
 }
 

@@ -19,8 +19,9 @@ hipError_t pra_layernorm_bwd(int dtype, const void* dy, const void* h, const voi
                              const float* rstd, const void* dres, void* dx, void* dwb, float* ws, int rows, int D,
                              int accumulate, hipStream_t s);
 
+// doc_start (optional, int32 [ntok]): packed sequences, table row (t % S) - doc_start[t]
 hipError_t pra_rope(int dtype, void* x, const void* tab, long ntok, int ld, int ncols, int D, int S,
-                    int pos_offset, int inverse, hipStream_t s);
+                    int pos_offset, int inverse, const int* doc_start, hipStream_t s);
 hipError_t pra_swiglu_fwd(int dtype, const void* g, const void* u, void* y, long ntok, int F, int ldg, int ldu,
                           int ldy, hipStream_t s);
 hipError_t pra_swiglu_bwd(int dtype, const void* dy, const void* g, const void* u, void* dg, void* du, long ntok,
@@ -105,6 +106,20 @@ hipError_t pra_attn_bwd_fused(int dtype, const void* q, const void* k, const voi
                               hipStream_t st);
 // floats of fp32 workspace pra_attn_bwd needs at `delta` (delta, row constants, split dK/dV parts)
 long pra_attn_bwd_workspace(int dtype, int B, int S, int Hq, int Hkv, int D);
+// Document-masked causal attention (attention_docs.hip), bf16 / fp16, S % 128 == 0. doc_start int32
+// [B][S]: query i sees key j iff doc_start[b][i] <= j <= i (values clamped into [0, i]). ws: fp32
+// workspace of pra_attn_docs_bwd_workspace words. rope_tab: inverse RoPE on dq / dk at the packed
+// positions i - doc_start[b][i]; skv: real sequence length of a zero-padded one. mid_event is
+// recorded between the dQ and dK/dV kernels.
+hipError_t pra_attn_docs_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
+                             const int* doc_start, int B, int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv,
+                             long ldo, float scale, hipStream_t st);
+hipError_t pra_attn_docs_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
+                             const float* lse, float* ws, void* dq, void* dk, void* dv, const int* doc_start, int B,
+                             int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo,
+                             long lddq, long lddk, long lddv, float scale, int skv, const float* rope_tab,
+                             hipEvent_t mid_event, hipStream_t st);
+long pra_attn_docs_bwd_workspace(int B, int S, int Hq, int Hkv, int D);
 // fp32 flash attention (attention_f32.hip, f32-input MFMA); pra_attn_fwd / pra_attn_bwd route kF32 here
 hipError_t pra_attn_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int B, int S, int Hq,
                             int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int skv,

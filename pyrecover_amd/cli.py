@@ -93,6 +93,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n-layers", type=int, default=None, help="override the preset's layer count")
     p.add_argument("--vocab-size", type=int, default=None, help="override vocab (default: tokenizer/preset)")
     p.add_argument("--synthetic-data", action="store_true", help="deterministic random tokens instead of parquet")
+    p.add_argument("--pack-sequences", action="store_true",
+                   help="concatenate the documents into one token stream and cut it into rows (no pad tokens); "
+                        "attention stays inside each document and RoPE positions restart (document-masked HIP "
+                        "attention kernels for bf16/fp16). With --synthetic-data: random document lengths")
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--num-workers", type=int, default=2, help="DataLoader workers (tokenization off the hot loop)")
     p.add_argument("--bucket-cap-mb", type=_bucket_arg, default=256.0,

@@ -8,7 +8,8 @@ the flat AdamW, including the side-stream overlapped updates) into one hipGraph
 (``torch.cuda.CUDAGraph`` is hipGraph on ROCm) and replays it for every later step.
 
 What changes per step without re-capture:
-* the batch is copied into the graph's static input tensors;
+* the batch (and, for packed sequences, its ``doc_start``) is copied into the graph's static input
+  tensors;
 * learning rate and Adam bias corrections are uploaded to device memory
   (:meth:`FlatAdamW.begin_graph_step`) and read by the optimizer kernel;
 * checkpoint snapshot fences are applied to the stream *before* the replay (a captured graph
@@ -54,6 +55,7 @@ class StepGraph:
         self.graph = None
         self.static_x = None
         self.static_y = None
+        self.static_ds = None  # doc_start of a packed batch (int32), or None
         self.loss = None
         self.replays = 0
 
@@ -62,7 +64,10 @@ class StepGraph:
         return self.graph is not None
 
     def _eager_body(self):
-        loss = self.model(self.static_x, labels=self.static_y)
+        if self.static_ds is not None:
+            loss = self.model(self.static_x, labels=self.static_y, doc_start=self.static_ds)
+        else:
+            loss = self.model(self.static_x, labels=self.static_y)
         loss.backward()
         if self.reducer is not None:
             self.reducer.finish()
@@ -71,9 +76,11 @@ class StepGraph:
         self.opt.step()
         return loss
 
-    def _capture(self, x, y):
+    def _capture(self, x, y, doc_start=None):
         self.static_x = x.detach().clone()
         self.static_y = y.detach().clone()
+        if doc_start is not None:
+            self.static_ds = doc_start.detach().to(torch.int32).contiguous().clone()
         self.opt.enable_graph_mode()
         self.opt.begin_graph_step()
         self.opt.zero_grad()  # host-side "fresh" flags decide which kernels get recorded
@@ -89,13 +96,18 @@ class StepGraph:
             self.opt.pre_update_fences = saved
         self.graph = g
 
-    def step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """Run one training step on batch (x, y); returns the (static) loss tensor."""
+    def step(self, x: torch.Tensor, y: torch.Tensor, doc_start=None) -> torch.Tensor:
+        """Run one training step on batch (x, y[, doc_start]); returns the (static) loss tensor.
+        Whether the batches are packed is fixed at capture."""
         if self.graph is None:
-            self._capture(x, y)  # capture records but does not execute: replay below runs it
+            self._capture(x, y, doc_start)  # capture records but does not execute: replay below runs it
         else:
+            if (doc_start is None) != (self.static_ds is None):
+                raise ValueError("StepGraph: doc_start must be given on every step or on none")
             self.static_x.copy_(x, non_blocking=True)
             self.static_y.copy_(y, non_blocking=True)
+            if doc_start is not None:
+                self.static_ds.copy_(doc_start, non_blocking=True)
             self.opt.begin_graph_step()
         for f in self.fences:
             f()

@@ -74,18 +74,20 @@ class Attention(nn.Module):
         self.wo = nn.Linear(args.n_heads * self.head_dim, args.dim, bias=False)
         self.use_flash_attention = args.use_flash_attention  # accepted for CLI parity; HIP flash always used on GPU
 
-    def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Standalone module forward with the reference signature (reference model.py:194-230):
         QKV projections, RoPE from ``freqs_cis`` (complex [>=S, head_dim/2]), causal GQA
         attention, output projection. Runs the same fused op as :class:`Transformer` (one QKV
-        GEMM, in-place RoPE, HIP flash attention); weight gradients accumulate into ``.grad``."""
+        GEMM, in-place RoPE, HIP flash attention); weight gradients accumulate into ``.grad``.
+        ``doc_start`` ([B, S]): packed sequences (see :meth:`Transformer.forward`)."""
         B, S, _ = x.shape
         qkv = [self.wq.weight, self.wk.weight, self.wv.weight]
         tab = rope_table(freqs_cis[:S].to(x.device))
         dims = (B, S, self.n_heads, self.n_kv_heads, self.head_dim, True)
         return F.attention_block(x, torch.cat([w.detach() for w in qkv], 0), self.wo.weight.detach(),
                                  F.UnflatSlot(qkv), F.UnflatSlot([self.wo.weight]), tab, dims,
-                                 qkv + [self.wo.weight])
+                                 qkv + [self.wo.weight], doc_start=F.as_doc_start(doc_start, B, S, x.device))
 
 
 class FeedForward(nn.Module):
@@ -123,10 +125,12 @@ class TransformerBlock(nn.Module):
             return F.add_layer_norm(x, delta, mod.weight, mod.bias, F.UnflatSlot([mod.weight, mod.bias]), mod.eps)
         return F.add_rms_norm(x, delta, mod.weight, F.UnflatSlot([mod.weight]), mod.eps)
 
-    def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor,
+                doc_start: Optional[torch.Tensor] = None) -> torch.Tensor:
         """h = x + attention(attention_norm(x)); out = h + feed_forward(ffn_norm(h))
         (reference model.py:325-327); the first residual add is fused into ffn_norm."""
-        h, n2 = self._norm(self.ffn_norm, x, self.attention(self._norm(self.attention_norm, x, None), freqs_cis))
+        h, n2 = self._norm(self.ffn_norm, x, self.attention(self._norm(self.attention_norm, x, None), freqs_cis,
+                                                            doc_start))
         return h + self.feed_forward(n2)
 
 
@@ -279,7 +283,7 @@ class Transformer(nn.Module):
             return F.add_layer_norm(x, delta, mod.weight, mod.bias, self._slot([mod.weight, mod.bias]), mod.eps)
         return F.add_rms_norm(x, delta, mod.weight, self._slot([mod.weight]), mod.eps)
 
-    def _block(self, layer, h, pending, B: int, S: int):
+    def _block(self, layer, h, pending, B: int, S: int, doc_start=None):
         """One TransformerBlock (reference model.py:325-327): returns (residual stream, the MLP
         output still to be added -- the add is fused into the next norm)."""
         a = self.model_args
@@ -292,7 +296,7 @@ class Transformer(nn.Module):
         qkv_p = [at.wq.weight, at.wk.weight, at.wv.weight]
         att = F.attention_block(n1, self._weight(qkv_p), self._weight([at.wo.weight]), self._slot(qkv_p),
                                 self._slot([at.wo.weight]), self.rope_tab, dims, qkv_p + [at.wo.weight],
-                                w_t=(self._weight_t(qkv_p), self._weight_t([at.wo.weight])))
+                                w_t=(self._weight_t(qkv_p), self._weight_t([at.wo.weight])), doc_start=doc_start)
         x2, n2 = self._norm(layer.ffn_norm, x, att)
         up = [ff.w1.weight, ff.w3.weight]
         mlp = F.swiglu_mlp(n2, self._weight(up), self._weight([ff.w2.weight]), self._slot(up),
@@ -300,11 +304,13 @@ class Transformer(nn.Module):
                            w_t=(self._weight_t(up), self._weight_t([ff.w2.weight])))
         return x2, mlp
 
-    def _trunk(self, tokens: torch.Tensor):
+    def _trunk(self, tokens: torch.Tensor, doc_start: Optional[torch.Tensor] = None):
         a = self.model_args
         B, S = tokens.shape
         if S > a.seq_len:
             raise ValueError(f"sequence length {S} exceeds model seq_len {a.seq_len}")
+        # once per step: every layer reads the same contiguous int32 [B, S] tensor
+        doc_start = F.as_doc_start(doc_start, B, S, tokens.device)
         emb = self.tok_embeddings.weight
         h = F.embedding(tokens, emb, self._slot([emb]))
         pending = None
@@ -314,19 +320,25 @@ class Transformer(nn.Module):
                 # keep only the block's inputs; its forward is re-run right before its backward
                 # (its weights are still un-updated then: a gradient bucket completes only after
                 # the lowest layer it covers has finished backward)
-                h, pending = torch.utils.checkpoint.checkpoint(self._block, layer, h, pending, B, S,
+                h, pending = torch.utils.checkpoint.checkpoint(self._block, layer, h, pending, B, S, doc_start,
                                                                use_reentrant=False)
             else:
-                h, pending = self._block(layer, h, pending, B, S)
+                h, pending = self._block(layer, h, pending, B, S, doc_start)
         if pending is None:
             return self._norm(self.norm, h, None)
         _, nf = self._norm(self.norm, h, pending)
         return nf
 
-    def forward(self, tokens: torch.Tensor, labels: Optional[torch.Tensor] = None, ignore_index: int = -100):
+    def forward(self, tokens: torch.Tensor, labels: Optional[torch.Tensor] = None, ignore_index: int = -100,
+                doc_start: Optional[torch.Tensor] = None):
         """logits (B, S, V) like the reference, or the mean causal-LM loss when labels are given
-        (fused output GEMM + cross-entropy, equal to reference train.py:263-266)."""
-        nf = self._trunk(tokens)
+        (fused output GEMM + cross-entropy, equal to reference train.py:263-266).
+
+        ``doc_start`` (integer [B, S], packed sequences): ``doc_start[b, i]`` is the index within row
+        ``b`` of the first token of token ``i``'s document. Token ``i`` attends to keys
+        ``doc_start[b, i] .. i`` only and its RoPE position is ``i - doc_start[b, i]``, so each
+        document is computed exactly as if it stood alone in a row of its own."""
+        nf = self._trunk(tokens, doc_start)
         W = self.output.weight
         if labels is not None:
             return F.linear_cross_entropy(nf, self._weight([W]), labels, self._slot([W]), W, ignore_index,

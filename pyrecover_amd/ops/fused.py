@@ -441,24 +441,36 @@ def _attn_hip(q, k):
                           and all(t.stride(-1) == 1 and t.stride(1) % 8 == 0 for t in (q, k)))
 
 
-def _attn_fwd(q, k, v, scale, causal):
+def _attn_docs_hip(q, k):
+    """The document-masked kernels (attention_docs.hip) are bf16/fp16 only: a packed fp32 or fp64
+    model runs the torch math of ops/reference.py."""
+    return _attn_hip(q, k) and _note_fallback("document-masked attention", q, q.element_size() == 2)
+
+
+def _attn_fwd(q, k, v, scale, causal, doc_start=None):
     """HIP flash attention for bf16/fp16/fp32 GPU tensors with head_dim 64/128 (any S: the binding
     zero-pads sequences that do not tile); otherwise (fp64, other head dims) torch math in the
     input's precision, as the reference's non-flash path (reference model.py:192, 227).
-    Returns (o, lse or None)."""
-    if _attn_hip(q, k):
+    doc_start (int32 [B, S], packed sequences): attention within each document only, on the
+    document-masked HIP kernels for bf16/fp16. Returns (o, lse or None)."""
+    if doc_start is not None:
+        if not causal:
+            raise ValueError("attention: doc_start implies causal attention")
+        if _attn_docs_hip(q, k):
+            return _ext.require_for(q).attn_fwd(q, k, v, scale, True, doc_start)
+    elif _attn_hip(q, k):
         return _ext.require_for(q).attn_fwd(q, k, v, scale, causal)
     ct = torch.promote_types(q.dtype, torch.float32)
     with torch.no_grad():
-        o = ref.attention_ref(q.to(ct), k.to(ct), v.to(ct), causal, scale)
+        o = ref.attention_ref(q.to(ct), k.to(ct), v.to(ct), causal, scale, doc_start=doc_start)
     return o.to(q.dtype).contiguous(), None
 
 
-def _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, scale, causal, rope_tab=None) -> bool:
+def _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, scale, causal, rope_tab=None, doc_start=None) -> bool:
     """Attention backward into dq/dk/dv. With ``rope_tab`` (the forward's RoPE table) the HIP kernels
-    store dq and dk with the inverse rotation already applied; returns whether that happened (the
-    torch path leaves it to the caller)."""
-    if lse is not None and _attn_hip(q, k):
+    store dq and dk with the inverse rotation already applied (at the packed positions when
+    ``doc_start`` is given); returns whether that happened (the torch path leaves it to the caller)."""
+    if lse is not None and (_attn_hip(q, k) if doc_start is None else _attn_docs_hip(q, k)):
         if q.dtype == torch.float32:
             rope_tab = None  # the fp32 kernels have no fused inverse RoPE: the caller applies it
         ev = None
@@ -466,14 +478,14 @@ def _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, scale, causal, rope_tab=None) -> 
             ev = torch.cuda.Event()
             ev.record()  # creates the event; the launcher re-records it between dQ and dK/dV
         _ext.require_for(q).attn_bwd(q, k, v, o, do, lse, dq, dk, dv, scale, causal, rope_tab,
-                                     ev.cuda_event if ev is not None else 0)
+                                     ev.cuda_event if ev is not None else 0, doc_start)
         if ev is not None:
             sched.attention_window(ev, q.device.index)
         return rope_tab is not None
     ct = torch.promote_types(q.dtype, torch.float32)
     with torch.enable_grad():
         qq, kk, vv = (t.detach().to(ct).requires_grad_() for t in (q, k, v))
-        out = ref.attention_ref(qq, kk, vv, causal, scale)
+        out = ref.attention_ref(qq, kk, vv, causal, scale, doc_start=doc_start)
         gq, gk, gv = torch.autograd.grad(out, (qq, kk, vv), do.to(ct))
     dq.copy_(gq)
     dk.copy_(gk)
@@ -482,31 +494,33 @@ def _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, scale, causal, rope_tab=None) -> 
 
 
 class _AttentionBlock(torch.autograd.Function):
-    """y = Wo · attn(rope(Wq x), rope(Wk x), Wv x) with a fused QKV GEMM."""
+    """y = Wo · attn(rope(Wq x), rope(Wk x), Wv x) with a fused QKV GEMM. doc_start (int32 [B, S] or
+    None): packed sequences -- RoPE positions restart and attention stays inside each document."""
 
     @staticmethod
-    def forward(ctx, x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, w_t, *params):
+    def forward(ctx, x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, w_t, doc_start, *params):
         B, S, Hq, Hkv, D, causal = dims
         ctx.w_t = w_t  # transposed weight shadows (or None): faster data-gradient GEMM layout
+        ctx.doc_start = doc_start
         T = B * S
         dim = x.shape[-1]
         x2 = x.reshape(T, dim)
         nq, nk = Hq * D, Hkv * D
-        if _nt_ok(x2, w_qkv, "qkv") and D % 8 == 0 and T % S == 0 and tab.is_contiguous():
+        if doc_start is None and _nt_ok(x2, w_qkv, "qkv") and D % 8 == 0 and T % S == 0 and tab.is_contiguous():
             # QKV projection with RoPE on q and k in the GEMM epilogue
             qkv = torch.empty(T, w_qkv.size(0), dtype=x2.dtype, device=x2.device)
             _ext.require_for(x2).gemm_nt_(x2, w_qkv, qkv, 3, None, tab, S, D, nq + nk)
         else:
             qkv = torch.mm(x2, w_qkv.t())
             if _ext.hip(qkv) and D % 8 == 0:
-                _ext.require_for(qkv).rope_(qkv, nq + nk, tab, D, S, 0, False)
+                _ext.require_for(qkv).rope_(qkv, nq + nk, tab, D, S, 0, False, doc_start)
             else:
-                ref.rope_inplace_2d(qkv, nq + nk, tab, D, S)
+                ref.rope_inplace_2d(qkv, nq + nk, tab, D, S, doc_start=doc_start)
         q = qkv[:, :nq].view(B, S, Hq, D)
         k = qkv[:, nq:nq + nk].view(B, S, Hkv, D)
         v = qkv[:, nq + nk:].view(B, S, Hkv, D)
         scale = 1.0 / math.sqrt(D)
-        o, lse = _attn_fwd(q, k, v, scale, causal)
+        o, lse = _attn_fwd(q, k, v, scale, causal, doc_start)
         o2 = o.view(T, nq)
         y = _mm_nt(o2, w_o, "o")
         ctx.save_for_backward(x2, qkv, o, lse, w_qkv, w_o, tab)
@@ -541,9 +555,13 @@ class _AttentionBlock(torch.autograd.Function):
         dv = dqkv[:, nq + nk:].view(B, S, Hkv, D)
         # the HIP backward applies the inverse RoPE to dq / dk in its epilogue (table rows = positions)
         use_tab = FUSED_ROPE_BWD and tab.is_contiguous() and tab.dtype == torch.float32 and tab.shape[0] >= S
-        fused_rope = _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, ctx.scale, causal, tab if use_tab else None)
+        doc_start = ctx.doc_start
+        fused_rope = _attn_bwd(q, k, v, o, do, lse, dq, dk, dv, ctx.scale, causal, tab if use_tab else None,
+                               doc_start)
+        # (the transposing inverse-RoPE kernel knows no documents: a packed batch whose dq / dk are
+        # still rotated takes rope_ + the plain transposes below)
         if (not _hip_wgrad_ok(dqkv, x2, "qkv") and TN_WGRAD and _tn_ok(dqkv) and _tn_ok(x2) and T % S == 0
-                and D % 8 == 0):
+                and D % 8 == 0 and (fused_rope or doc_start is None)):
             # (inverse RoPE in place +) dqkv^T in one pass, for the K-contiguous weight-grad GEMM
             C = _ext.require_for(dqkv)
             dqkvT = C.transpose2d(dqkv) if fused_rope else C.rope_t_(dqkv, nq + nk, tab, D, S, True)
@@ -553,19 +571,30 @@ class _AttentionBlock(torch.autograd.Function):
             if fused_rope:
                 pass  # dq / dk already un-rotated by the attention backward
             elif _ext.hip(dqkv) and D % 8 == 0:
-                _ext.require_for(dqkv).rope_(dqkv, nq + nk, tab, D, S, 0, True)
+                _ext.require_for(dqkv).rope_(dqkv, nq + nk, tab, D, S, 0, True, doc_start)
             else:
-                ref.rope_inplace_2d(dqkv, nq + nk, tab, D, S, inverse=True)
+                ref.rope_inplace_2d(dqkv, nq + nk, tab, D, S, inverse=True, doc_start=doc_start)
             dx = _mm_dgrad(dqkv, w_qkv, w_qkv_t, "qkv_d")
             _wgrad_into(slot_qkv, dqkv, x2, tuple(w_qkv.shape), "qkv")
-        n_params = ctx.needs_input_grad.__len__() - 8
-        return (dx.view(B, S, -1), None, None, None, None, None, None, None) + (None,) * n_params
+        n_params = ctx.needs_input_grad.__len__() - 9
+        return (dx.view(B, S, -1), None, None, None, None, None, None, None, None) + (None,) * n_params
 
 
-def attention_block(x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, params, w_t=None):
+def as_doc_start(doc_start, B: int, S: int, device):
+    """doc_start of a packed batch as the ops take it: contiguous int32 [B, S] on `device`."""
+    if doc_start is None:
+        return None
+    if tuple(doc_start.shape) != (B, S):
+        raise ValueError(f"doc_start must have shape {(B, S)}, got {tuple(doc_start.shape)}")
+    return doc_start.to(device=device, dtype=torch.int32).contiguous()
+
+
+def attention_block(x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, params, w_t=None, doc_start=None):
     if w_t is not None and any(t is None for t in w_t):
         w_t = None
-    return _AttentionBlock.apply(x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, w_t, *params)
+    if doc_start is not None and (doc_start.dtype != torch.int32 or not doc_start.is_contiguous()):
+        doc_start = as_doc_start(doc_start, dims[0], dims[1], x.device)
+    return _AttentionBlock.apply(x, w_qkv, w_o, slot_qkv, slot_o, tab, dims, w_t, doc_start, *params)
 
 
 # ---------------------------------------------------------------------------------------
@@ -723,21 +752,23 @@ def linear_cross_entropy(h, w_out, labels, slot, weight_param, ignore_index: int
 # Standalone user-facing ops (autograd, no slots)
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        o, lse = _attn_fwd(q, k, v, scale, causal)
+    def forward(ctx, q, k, v, causal, scale, doc_start):
+        o, lse = _attn_fwd(q, k, v, scale, causal, doc_start)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.doc_start = causal, scale, doc_start
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        _attn_bwd(q, k, v, o, do.contiguous(), lse, dq, dk, dv, ctx.scale, ctx.causal)
-        return dq, dk, dv, None, None
+        _attn_bwd(q, k, v, o, do.contiguous(), lse, dq, dk, dv, ctx.scale, ctx.causal, None, ctx.doc_start)
+        return dq, dk, dv, None, None, None
 
 
-def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None):
-    """Causal/full GQA attention on [B, S, H, D] tensors (HIP MFMA kernel on GPU)."""
+def flash_attention(q, k, v, causal: bool = True, scale: Optional[float] = None, doc_start=None):
+    """Causal/full GQA attention on [B, S, H, D] tensors (HIP MFMA kernel on GPU). doc_start ([B, S],
+    packed sequences): query i sees key j iff doc_start[b, i] <= j <= i (causal only)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    return _FlashAttention.apply(q, k, v, causal, scale)
+    doc_start = as_doc_start(doc_start, q.shape[0], q.shape[1], q.device)
+    return _FlashAttention.apply(q, k, v, causal, scale, doc_start)

@@ -64,13 +64,35 @@ def rmsnorm_bwd(dy, h, w, rstd, dres):
     return dx.reshape(h.shape), dw
 
 
+def doc_positions(doc_start: torch.Tensor) -> torch.Tensor:
+    """Packed sequences: int64 [B, S] position of each token within its document, i - doc_start[b, i]
+    with doc_start clamped into [0, i] (as the HIP kernels clamp it)."""
+    S = doc_start.shape[-1]
+    i = torch.arange(S, device=doc_start.device)
+    return i - torch.minimum(doc_start.long().clamp_min(0), i)
+
+
+def doc_mask(doc_start: torch.Tensor) -> torch.Tensor:
+    """bool [B, 1, S, S], True where query i may NOT see key j: visible iff doc_start[b, i] <= j <= i."""
+    S = doc_start.shape[-1]
+    i = torch.arange(S, device=doc_start.device)
+    lo = torch.minimum(doc_start.long().clamp_min(0), i)  # [B, S]
+    j = i.view(1, 1, S)
+    return ((j > i.view(1, S, 1)) | (j < lo.unsqueeze(-1))).unsqueeze(1)
+
+
 def rope_inplace_2d(x2d: torch.Tensor, ncols: int, tab: torch.Tensor, head_dim: int, seq_len: int,
-                    inverse: bool = False):
-    """Rotate the first `ncols` columns of every row (heads of size head_dim), interleaved pairs."""
+                    inverse: bool = False, doc_start: Optional[torch.Tensor] = None):
+    """Rotate the first `ncols` columns of every row (heads of size head_dim), interleaved pairs.
+    doc_start ([B, S], packed sequences): token i of a row takes table row i - doc_start[b, i]."""
     T = x2d.shape[0]
     v = up(x2d[:, :ncols]).reshape(T // seq_len, seq_len, ncols // head_dim, head_dim // 2, 2)
-    c = tab[:seq_len, :, 0].view(1, seq_len, 1, head_dim // 2)
-    s = tab[:seq_len, :, 1].view(1, seq_len, 1, head_dim // 2)
+    if doc_start is not None:
+        rows = tab[doc_positions(doc_start.reshape(T // seq_len, seq_len))].to(v.dtype)  # [B, S, D/2, 2]
+        c, s = rows[..., 0].unsqueeze(2), rows[..., 1].unsqueeze(2)
+    else:
+        c = tab[:seq_len, :, 0].view(1, seq_len, 1, head_dim // 2)
+        s = tab[:seq_len, :, 1].view(1, seq_len, 1, head_dim // 2)
     if inverse:
         s = -s
     a, b = v[..., 0], v[..., 1]
@@ -88,19 +110,25 @@ def apply_rotary_emb_ref(xq, xk, freqs_cis):
     return xq_out.type_as(xq), xk_out.type_as(xk)
 
 
-def attention_ref(q, k, v, causal: bool = True, scale: Optional[float] = None):
-    """[B, S, H, D] in/out; GQA by repeating kv heads (reference model.py:130-139, 217-229)."""
+def attention_ref(q, k, v, causal: bool = True, scale: Optional[float] = None,
+                  doc_start: Optional[torch.Tensor] = None):
+    """[B, S, H, D] in/out; GQA by repeating kv heads (reference model.py:130-139, 217-229).
+    doc_start ([B, S], packed sequences): causal within each document only."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     if Hkv != Hq:
         k = k.repeat_interleave(Hq // Hkv, dim=2)
         v = v.repeat_interleave(Hq // Hkv, dim=2)
+    if doc_start is not None:
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+                                           attn_mask=~doc_mask(doc_start), scale=scale)
+        return o.transpose(1, 2).contiguous()
     o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
                                        is_causal=causal, scale=scale)
     return o.transpose(1, 2).contiguous()
 
 
-def attention_lse_ref(q, k, v, causal=True, scale=None):
+def attention_lse_ref(q, k, v, causal=True, scale=None, doc_start=None):
     """fp32 attention output + natural-log LSE [B, H, S] (oracle for the HIP kernel)."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
@@ -108,7 +136,9 @@ def attention_lse_ref(q, k, v, causal=True, scale=None):
     kk = up(k).repeat_interleave(Hq // Hkv, dim=2)
     vv = up(v).repeat_interleave(Hq // Hkv, dim=2)
     s = torch.einsum("bqhd,bkhd->bhqk", up(q), kk) * scale
-    if causal:
+    if doc_start is not None:
+        s = s.masked_fill(doc_mask(doc_start), float("-inf"))
+    elif causal:
         m = torch.ones(S, S, dtype=torch.bool, device=q.device).triu(1)
         s = s.masked_fill(m, float("-inf"))
     lse = torch.logsumexp(s, dim=-1)

@@ -33,7 +33,8 @@ from .ckpt.sharded import finalize_pending, load_ckpt_distributed, save_ckpt_dis
 from .ckpt.vanilla import load_ckpt_vanilla, save_ckpt_vanilla
 from .cli import PRECISION_STR_TO_DTYPE, set_default_dtype
 from .config import get_preset
-from .data.dataset import CollatorForCLM, ParquetDataset, SyntheticTokenDataset
+from .data.dataset import (CollatorForCLM, CollatorForPackedCLM, PackedParquetDataset, ParquetDataset,
+                           SyntheticTokenDataset)
 from .data.sampler import ResumableDistributedSampler
 from .data.tokenizer import load_tokenizer
 from .models.llama import Transformer
@@ -186,15 +187,21 @@ def train(args):
     accum = max(1, int(getattr(args, "grad_accumulation_steps", 1) or 1))
     n_samples = args.batch_size * args.training_steps * accum
     preset = get_preset(args.model_preset)
+    pack = bool(getattr(args, "pack_sequences", False))
     if args.synthetic_data:
         vocab = args.vocab_size or preset.vocab_size
         pad_id = 0
-        train_ds = SyntheticTokenDataset(vocab, seq_len, n_samples, seed=args.seed, pad_token_id=pad_id)
+        # --pack-sequences: rows of several random-length documents (same tokens as without it)
+        train_ds = SyntheticTokenDataset(vocab, seq_len, n_samples, seed=args.seed, pad_token_id=pad_id,
+                                         doc_len_range=(max(1, seq_len // 16), max(1, seq_len // 2)) if pack else None)
     else:
         tokenizer = load_tokenizer(args.tokenizer_name_or_path)
-        train_ds = ParquetDataset(args.dataset, tokenizer, seq_len, n_samples)
+        train_ds = (PackedParquetDataset if pack else ParquetDataset)(args.dataset, tokenizer, seq_len, n_samples)
         vocab = args.vocab_size or tokenizer.vocab_size
         pad_id = tokenizer.pad_token_id
+    if pack:
+        log_rank0("Packed sequences: rows hold whole documents back to back (no padding); attention and RoPE "
+                  "positions stay inside each document")
     log_rank0(f"Global batch size: {global_batch_size}\nLocal batch size: {local_batch_size}")
     if local_batch_size * world_size != global_batch_size:
         # reference train.py:62-63 keeps max(B//W,1) per rank but counts B·S tokens per step
@@ -207,7 +214,7 @@ def train(args):
                   f"({global_batch_size * accum} sequences per optimizer step)")
     train_sampler = ResumableDistributedSampler(len(train_ds), num_replicas=world_size, rank=rank, shuffle=True,
                                                 seed=args.seed)
-    train_collator = CollatorForCLM(seq_len, pad_id)
+    train_collator = (CollatorForPackedCLM if pack else CollatorForCLM)(seq_len, pad_id)
     train_dl = DataLoader(train_ds, batch_size=local_batch_size, collate_fn=train_collator, sampler=train_sampler,
                           num_workers=args.num_workers, pin_memory=use_cuda,
                           persistent_workers=False)
@@ -309,6 +316,9 @@ def train(args):
 
     ntokens_since_last_log = 0
     ntraining_tokens_since_last_log = 0
+    nonpad_since_last_log = 0  # input positions that are not padding
+    docs_since_last_log = 0  # documents (packed: starts of documents; else one per row)
+    rows_since_last_log = 0
     time_last_log = time.perf_counter()
 
     # ---------------- checkpoint dirs / CSV (reference train.py:135-161) ----------------
@@ -450,19 +460,30 @@ def train(args):
         for _ in range(accum):
             train_sampler.set_epoch(epoch)
             try:
-                input_ids, labels = next(train_dl_iterator)
+                batch = next(train_dl_iterator)
             except StopIteration:
                 epoch += 1
                 train_sampler.set_epoch(epoch)
                 train_dl_iterator = iter(train_dl)
-                input_ids, labels = next(train_dl_iterator)
+                batch = next(train_dl_iterator)
+            input_ids, labels = batch[0], batch[1]
+            doc_start = batch[2] if len(batch) > 2 else None  # packed loader: (inputs, labels, doc_start)
             train_sampler.advance(input_ids.shape[0])
+            rows_since_last_log += input_ids.shape[0]
+            if doc_start is not None:
+                pos = torch.arange(doc_start.shape[1], dtype=doc_start.dtype)
+                docs_since_last_log += int((doc_start == pos).sum())
+                nonpad_since_last_log += input_ids.numel()
+            else:
+                docs_since_last_log += input_ids.shape[0]
+                nonpad_since_last_log += int(input_ids.ne(pad_id).sum()) if pad_id is not None else input_ids.numel()
 
             # true tokens of this step on all ranks (every rank runs the same local batch)
             ntokens_since_last_log += input_ids.shape[0] * world_size * seq_len
             num_items_in_batch = labels.ne(-100).sum()
             ntraining_tokens_since_last_log += int(num_items_in_batch) * world_size
-            micro.append((input_ids.to(device, non_blocking=True), labels.to(device, non_blocking=True)))
+            micro.append((input_ids.to(device, non_blocking=True), labels.to(device, non_blocking=True),
+                          doc_start.to(device, non_blocking=True) if doc_start is not None else None))
 
         if step_graph is not None and eager_steps_this_run >= args.compile_warmup_steps:
             loss = step_graph.step(*micro[0])  # fences the snapshot before the replay
@@ -471,13 +492,14 @@ def train(args):
                 comm_timer.begin_step()
             optimizer.zero_grad()
             loss = None
-            for m, (input_ids, labels) in enumerate(micro):
+            for m, (input_ids, labels, doc_start) in enumerate(micro):
                 if m:
                     flat.next_micro_batch()  # producers now add into the written gradients
                 if reducer is not None:
                     # no communication (or overlapped update) until the last micro-batch
                     reducer.enabled = m == accum - 1
-                lm = model(input_ids, labels=labels)
+                lm = (model(input_ids, labels=labels) if doc_start is None
+                      else model(input_ids, labels=labels, doc_start=doc_start))
                 lm.backward()
                 loss = lm.detach() if loss is None else loss + lm.detach()
             if accum > 1:
@@ -511,6 +533,8 @@ def train(args):
             if metrics_f is not None:
                 rec = {"step": train_step, "epoch": epoch, "loss": lval, "tokens_per_s": tps,
                        "tokens_per_s_per_gpu": per_gpu, "mfu_pct": mfu, "tflops_per_gpu": tflops,
+                       "docs_per_row": docs_since_last_log / max(rows_since_last_log, 1),
+                       "nonpad_fraction": nonpad_since_last_log / max(rows_since_last_log * seq_len, 1),
                        "time": time.time()}
                 rec.update(_diagnostics(step_timer, device, comm_timer, world_size, ckpt_window, stopper))
                 metrics_f.write(json.dumps(rec) + "\n")
@@ -520,6 +544,7 @@ def train(args):
             ckpt_window.clear()
             ntokens_since_last_log = 0
             ntraining_tokens_since_last_log = 0
+            nonpad_since_last_log = docs_since_last_log = rows_since_last_log = 0
             time_last_log = time.perf_counter()
 
         if is_dist and check_every > 0 and train_step % check_every == 0:

@@ -13,7 +13,7 @@
 #   --distributed --exp_name=NAME --continue --use_torch_distributed_ckpt --timeaware-checkpointing
 #   --use_flash_attention --log-loss-to-csv --fused-optimizer --compile --sequence-length=N
 #   --profile-nsys (rocprofv3 on MI355X)
-# plus: --async-checkpoint, --resubmit=requeue|chain, --model-preset=NAME, --synthetic-data,
+# plus: --async-checkpoint, --resubmit=requeue|chain, --model-preset=NAME, --synthetic-data, --pack-sequences,
 #       --batch-size=N, --training-steps=N
 #       --checkpoint-dir=DIR, --max-resubmits=N
 # Fixes vs the reference: --sequence-length is passed with its flag name, the
@@ -71,6 +71,7 @@ for arg in "$@"; do
     --training-steps=*) TRAINING_STEPS="${arg#*=}" ;;
     --model-preset=*) EXTRA+=(--model-preset "${arg#*=}") ;;
     --synthetic-data) EXTRA+=(--synthetic-data) ;;
+    --pack-sequences) EXTRA+=(--pack-sequences) ;;
     --async-checkpoint) EXTRA+=(--async-checkpoint) ;;
     --resubmit=*) EXTRA+=(--resubmit "${arg#*=}" --resubmit-script "$0") ;;
     --max-resubmits=*) EXTRA+=(--max-resubmits "${arg#*=}") ;;

@@ -4,6 +4,11 @@ bench shape (default B=4, S=2048, Hq=Hkv=32, D=128, causal), on random data (rul
 
 FLOP convention (causal halves): fwd 4*B*H*S^2*D/2, bwd (dkdv + dq kernels, recompute included)
 14*B*H*S^2*D/2 -- the work the kernels actually do -- and the "model" bwd convention 10*... .
+
+--docs N [N ...]: also time the document-masked kernels (csrc/kernels/attention_docs.hip) with N equal
+documents per row, next to the default causal kernels in the same process: the arms alternate over
+--rounds rounds (each a warmed window of --iters calls) and the median per arm is printed, one JSON
+line each, with the visible share of the causal area (1 / N) and the time relative to the causal arm.
 """
 import argparse
 import json
@@ -25,6 +30,9 @@ def main():
     ap.add_argument("--D", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--noncausal", action="store_true")
+    ap.add_argument("--docs", type=int, nargs="+", default=None,
+                    help="equal documents per row for the document-masked kernels (S %% N == 0)")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds per arm (--docs)")
     a = ap.parse_args()
     from pyrecover_amd import _ext
 
@@ -65,6 +73,35 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.iters
 
+    if a.docs:
+        import statistics
+
+        if not causal or any(n <= 0 or S % n for n in a.docs):
+            raise SystemExit("--docs: causal only, and S must be a multiple of every N")
+        arms = {"causal": (fwd, bwd, o, lse)}
+        for n in a.docs:
+            ds = ((torch.arange(S, device=dev, dtype=torch.int32) // (S // n)) * (S // n)).repeat(B, 1).contiguous()
+            on, ln = C.attn_fwd(q, k, v, scale, True, ds)
+            arms[f"docs{n}"] = (lambda ds=ds: C.attn_fwd(q, k, v, scale, True, ds),
+                                lambda ds=ds, on=on, ln=ln: C.attn_bwd(q, k, v, on, do, ln, dq, dk, dv, scale, True,
+                                                                       None, 0, ds), on, ln)
+        times = {name: ([], []) for name in arms}
+        for r in range(a.rounds):
+            names = list(arms) if r % 2 == 0 else list(arms)[::-1]
+            for name in names:
+                times[name][0].append(timeit(arms[name][0]))
+                times[name][1].append(timeit(arms[name][1]))
+        base_f, base_b = (statistics.median(t) for t in times["causal"])
+        for name, (tfs, tbs) in times.items():
+            mf, mb = statistics.median(tfs), statistics.median(tbs)
+            n = 1 if name == "causal" else int(name[4:])
+            rec = {"arm": name, "shape": dict(B=B, S=S, Hq=Hq, Hkv=Hkv, D=D), "visible_area": round(1 / n, 4),
+                   "fwd_ms": round(mf, 4), "bwd_ms": round(mb, 4),
+                   "fwd_min_max": [round(min(tfs), 4), round(max(tfs), 4)],
+                   "bwd_min_max": [round(min(tbs), 4), round(max(tbs), 4)],
+                   "fwd_vs_causal": round(mf / base_f, 3), "bwd_vs_causal": round(mb / base_b, 3)}
+            print(json.dumps(rec), flush=True)
+        return
     tf = timeit(fwd)
     tb = timeit(bwd)
     frac = 0.5 if causal else 1.0

@@ -28,7 +28,8 @@ def parse_arm(spec):
     """`opt.ATTR=value` sets an attribute of the optimizer instance; `attn.OPTION=value` an
     attention kernel option (_ext.set_attn_options); `native.SETTER=value` calls that setter of the
     extension before the arm's steps and with 0 after them; the item `noupdate` skips the AdamW update
-    kernels (a diagnostic arm: what the optimizer costs the step)."""
+    kernels (a diagnostic arm: what the optimizer costs the step); the item `docs=N` runs the arm's
+    steps on packed batches of N equal documents per row (doc_start: document-masked attention)."""
     name, _, body = spec.partition(":")
     sets = []
     for item in filter(None, body.split(";")):
@@ -36,6 +37,9 @@ def parse_arm(spec):
             sets.append(("opt", "_update_range", "noupdate"))
             continue
         lhs, _, rhs = item.partition("=")
+        if lhs.strip() == "docs":
+            sets.append(("docs", "docs", int(rhs)))
+            continue
         mod, _, attr = lhs.strip().rpartition(".")
         if mod in ("attn", "native"):  # attention option / native setter C.<attr>(value), reset to 0 after
             sets.append((mod, attr, ast.literal_eval(rhs.strip())))
@@ -81,10 +85,15 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
 
-    def step():
+    def step(docs=0):
         t = torch.randint(0, cfg.vocab_size, (B, S + 1), device=dev, generator=gen)
         opt.zero_grad()
-        loss = model(t[:, :-1], labels=t[:, 1:])
+        if docs:
+            n = S // docs
+            ds = ((torch.arange(S, device=dev, dtype=torch.int32) // n) * n).repeat(B, 1)
+            loss = model(t[:, :-1], labels=t[:, 1:], doc_start=ds)
+        else:
+            loss = model(t[:, :-1], labels=t[:, 1:])
         loss.backward()
         reducer.finish()
         opt.step()
@@ -95,7 +104,7 @@ def main():
     def resolve(sets):
         out = []
         for m, k, v in sets:
-            if m in ("attn", "native"):
+            if m in ("attn", "native", "docs"):
                 continue
             m = opt if m == "opt" else m
             if v == "noupdate":
@@ -106,6 +115,7 @@ def main():
     def run(arm, n):
         attn = {k: v for m, k, v in arm[1] if m == "attn"}
         prev_attn = _ext.set_attn_options(**attn) if attn else None
+        docs = max([v for m, _, v in arm[1] if m == "docs"] or [0])
         natives = [(k, v) for m, k, v in arm[1] if m == "native"]
         for k, v in natives:
             getattr(_ext.native(), k)(v)
@@ -117,7 +127,7 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(n):
-                loss = step()
+                loss = step(docs)
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1000 / n, float(loss.item())
         finally:
