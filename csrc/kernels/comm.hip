@@ -1,4 +1,4 @@
-// Reduction kernel of the intra-node xGMI all-reduce (csrc/dist/xgmi.cpp, pyrecover_amd/parallel/
+// Reduction kernel of the intra-node xGMI all-reduce (csrc/comm/xgmi.cpp, pyrecover_amd/parallel/
 // xgmi.py): dst = src_0 + src_1 + ... + src_{W-1}, summed in fp32 in rank order and rounded
 // once, so every rank reduces its slice identically (bit-reproducible, unlike a ring that rounds
 // at every hop). The sources are this rank's own slice and the peers' slices, read straight from
@@ -94,7 +94,7 @@ extern "C" hipError_t pra_copy_d2d(void* dst, const void* src, long nbytes, hipS
   return hipGetLastError();
 }
 
-// All-gather phase of the pull all-reduce (csrc/dist/xgmi.cpp XgmiEngine): every peer's reduced
+// All-gather phase of the pull all-reduce (csrc/comm/xgmi.cpp XgmiEngine): every peer's reduced
 // slice is pulled from its IPC-mapped buffer into this rank's buffer in ONE kernel, the W - 1 source
 // GPUs spread over blockIdx.y, so the pulls from all peers (all xGMI links) run at once. Slices are
 // 16-B aligned (8-element cuts); a tail of n % 16 bytes is copied bytewise by the last block row.
@@ -143,6 +143,102 @@ extern "C" hipError_t pra_pull_gather(const void* const* srcs, void* const* dsts
   if (bx > 512) bx = 512;
   if (bx < 1) bx = 1;
   hipLaunchKernelGGL(pra::pull_gather_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, s, l);
+  return hipGetLastError();
+}
+
+// Sparse embedding-gradient exchange of the xGMI engine (csrc/comm/xgmi.cpp, --sparse-embedding-grad):
+// every rank publishes its step's token ids, sorted (n entries, duplicates allowed, entries outside
+// [0, V) skipped), and the rows of the ids' union are reduced in the ranks' IPC-mapped dense [V, D]
+// gradients in place: no vocab-sized scratch, no staged rows.
+//   Row owner: rank q owns rows [V q / W, V (q + 1) / W), i.e. owner(id) = ((id + 1) W - 1) / V: a pure
+//   function of id, V and W, the same on every rank.
+//   One wave per list entry (rank r, position i). An entry stands for its id when it is the id's first
+//   occurrence in list r (previous entry differs) and no lower rank's list holds the id (binary
+//   search), so every id of the union is handled by exactly one wave.
+//   PHASE 1 (owner only): sum the id's row over the ranks whose list holds it, in rank order, in fp32,
+//   one rounding, into this rank's buffer. A rank writes only rows it owns and reads only rows it
+//   owns, so no rank reads a row another one writes.
+//   PHASE 2 (after every owner's phase 1): copy each union row this rank does not own from its owner.
+// 16 B per lane along D (D % 8 == 0), plain vector stores, no atomics.
+namespace pra {
+struct SparseLists {
+  void* grad[16];
+  const int64_t* ids[16];
+};
+
+__device__ __forceinline__ bool list_holds(const int64_t* __restrict__ l, long n, int64_t id) {
+  long lo = 0, hi = n;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (l[mid] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && l[lo] == id;
+}
+
+template <typename T, int PHASE>
+__global__ __launch_bounds__(256) void sparse_rows_kernel(SparseLists l, int W, int me, long n, long V, long D) {
+  const long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (e >= (long)W * n) return;
+  const int r = (int)(e / n);
+  const long i = e - (long)r * n;
+  const int64_t id = l.ids[r][i];
+  if (id < 0 || id >= V) return;
+  if (i > 0 && l.ids[r][i - 1] == id) return;
+  const int owner = (int)(((id + 1) * W - 1) / V);
+  if (PHASE == 1 ? owner != me : owner == me) return;
+  for (int q = 0; q < r; ++q)
+    if (list_holds(l.ids[q], n, id)) return;
+  const int lane = threadIdx.x & 63;
+  T* dst = reinterpret_cast<T*>(l.grad[me]) + id * D;
+  if (PHASE == 1) {
+    unsigned has = 0u;
+    for (int q = r + 1; q < W; ++q)
+      if (list_holds(l.ids[q], n, id)) has |= 1u << q;
+    for (long c = lane; c < D / 8; c += 64) {
+      float acc[8], v[8];
+      load8<T>(reinterpret_cast<const T*>(l.grad[r]) + id * D + c * 8, acc);
+      for (int q = r + 1; q < W; ++q) {
+        if (!((has >> q) & 1u)) continue;
+        load8<T>(reinterpret_cast<const T*>(l.grad[q]) + id * D + c * 8, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] += v[j];
+      }
+      store8<T>(dst + c * 8, acc);
+    }
+  } else {
+    const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const T*>(l.grad[owner]) + id * D);
+    uint4* d16 = reinterpret_cast<uint4*>(dst);
+    const long n16 = D * (long)sizeof(T) / 16;
+    for (long c = lane; c < n16; c += 64) d16[c] = src[c];
+  }
+}
+}  // namespace pra
+
+// grads[r]: rank r's [V, D] gradient (16-B aligned); ids[r]: its n sorted int64 ids; phase 1 or 2
+extern "C" hipError_t pra_sparse_rows(int dtype, int phase, void* const* grads, const int64_t* const* ids, int W, int me,
+                                      long n, long V, long D, hipStream_t s) {
+  if (W < 1 || W > 16 || me < 0 || me >= W || (phase != 1 && phase != 2)) return hipErrorInvalidValue;
+  if (n < 0 || V < 1 || D < 8 || D % 8) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  pra::SparseLists l{};
+  for (int r = 0; r < W; ++r) {
+    if (reinterpret_cast<uintptr_t>(grads[r]) % 16 || reinterpret_cast<uintptr_t>(ids[r]) % 8 || !grads[r] || !ids[r])
+      return hipErrorInvalidValue;
+    l.grad[r] = grads[r];
+    l.ids[r] = ids[r];
+  }
+  const long blocks = ((long)W * n + 3) / 4;
+  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  if (phase == 1) {
+    PRA_DISPATCH_FLOAT(dtype, T,
+                       hipLaunchKernelGGL((pra::sparse_rows_kernel<T, 1>), dim3((unsigned)blocks), dim3(256), 0, s, l, W,
+                                          me, n, V, D));
+  } else {
+    PRA_DISPATCH_FLOAT(dtype, T,
+                       hipLaunchKernelGGL((pra::sparse_rows_kernel<T, 2>), dim3((unsigned)blocks), dim3(256), 0, s, l, W,
+                                          me, n, V, D));
+  }
   return hipGetLastError();
 }
 

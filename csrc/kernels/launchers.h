@@ -79,6 +79,10 @@ hipError_t pra_checksum(int dtype, const void* x, long nbytes, double* ws_sum, u
 hipError_t pra_sum_slices(int dtype, const void* const* srcs, int nsrc, void* dst, long n, hipStream_t s);
 // n (<= 16) copies src[k] -> dst[k] of nbytes[k] in one kernel (16-B aligned pointers)
 hipError_t pra_pull_gather(const void* const* srcs, void* const* dsts, const long* nbytes, int n, hipStream_t s);
+// sparse embedding-gradient exchange over W (<= 16) dense [V, D] gradients and W sorted id lists of n
+// int64 entries: phase 1 reduces the union rows rank `me` owns into grads[me], phase 2 copies the others
+hipError_t pra_sparse_rows(int dtype, int phase, void* const* grads, const int64_t* const* ids, int W, int me, long n,
+                           long V, long D, hipStream_t s);
 
 hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
                        double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,

@@ -104,15 +104,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "bandwidth at startup and pick the size (parallel/bucket_tune.py)")
     p.add_argument("--allreduce", choices=["rccl", "xgmi"], default="rccl",
                    help="gradient all-reduce backend: RCCL rings (default) or the direct per-link xGMI "
-                        "reduce-scatter/all-gather over IPC-mapped peer buffers (single node)")
+                        "reduce-scatter/all-gather over IPC-mapped peer buffers (single node); it also runs "
+                        "--shard-optimizer and --sparse-embedding-grad on its own kernels")
     p.add_argument("--shard-optimizer", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                    help="ZeRO-1 data parallelism: reduce-scatter each gradient bucket, update only this rank's "
                         "1/W of the parameters, all-gather them (replicated parameters, unchanged checkpoints); "
                         "auto: at W > 1 for 16-bit GPU models that carry no transposed weight shadows at this "
-                        "batch (e.g. Llama-3-8B S2048 B1); a bare flag means on")
+                        "batch (e.g. Llama-3-8B S2048 B1); a bare flag means on; works with either --allreduce "
+                        "backend")
     p.add_argument("--sparse-embedding-grad", choices=["auto", "on", "off"], default="auto",
                    help="reduce the token-embedding gradient as (token id, row) pairs instead of a dense "
-                        "all-reduce; auto: when the ranks' tokens per step are at most half the vocabulary")
+                        "all-reduce; auto: when the ranks' tokens per step are at most half the vocabulary; with "
+                        "--allreduce xgmi: HIP kernels over the peers' mapped gradients, only the ids are exchanged")
     p.add_argument("--replica-check-every", type=int, default=None,
                    help="W > 1: compare a checksum of the parameters (and optimizer moments) across ranks every "
                         "N steps and at the end, and stop on a mismatch (default 10 x --logging-frequency; 0 = off)")

@@ -251,6 +251,9 @@ class FlatAdamW(torch.optim.AdamW):
         for w in self._gathers:
             w.wait()
         self._gathers = []
+        r = getattr(self.flat, "reducer", None)
+        if r is not None:
+            r.gathers_done()  # xGMI engine: its step barrier goes behind the parameter gathers
         self.flat.refresh_transposed()
 
     def gather_state(self):

@@ -46,7 +46,13 @@ class GradReducer:
     ``sparse_slot`` (``--sparse-embedding-grad``): the index of the embedding's gradient slot. It
     gets a bucket of its own, and instead of a dense all-reduce of the (vocab x dim) gradient, where
     at most B*S rows per rank are non-zero, the ranks exchange (token id, row) pairs
-    (:meth:`_sparse_exchange`)."""
+    (:meth:`_sparse_exchange`).
+
+    Both modes also run on ``backend="xgmi"``, on the engine's own kernels: the reduce-scatter is its
+    pull-reduce alone, :meth:`gather_params` one pull-gather per bucket from the peers' mapped
+    parameter buffers, and the sparse bucket is reduced row by row in the mapped dense gradients from
+    the ranks' published id lists (:meth:`XgmiAllReduce.launch_sparse`; no vocab-sized scratch). The
+    engine's step barrier then follows the parameter gathers (:meth:`gathers_done`)."""
 
     def __init__(self, flat: FlatParams, group=None, bucket_cap_mb: float = 256.0, first_bucket_mb: float = 64.0,
                  backend: str = "rccl", shard: bool = False, sparse_slot: Optional[int] = None):
@@ -57,12 +63,8 @@ class GradReducer:
         if backend not in ("rccl", "xgmi"):
             raise ValueError(f"unknown all-reduce backend {backend!r}")
         self.backend = backend if self.world > 1 else "rccl"
-        if shard and self.backend == "xgmi":
-            raise ValueError("--shard-optimizer runs on RCCL reduce-scatter / all-gather: use --allreduce rccl")
         self.shard = bool(shard) and self.world > 1
         self.sparse_slot = sparse_slot if self.world > 1 else None
-        if self.sparse_slot is not None and self.backend == "xgmi":
-            raise ValueError("--sparse-embedding-grad runs on RCCL all-gathers: use --allreduce rccl")
         self.hooks = []
         esz = flat.grad.element_size()
         cap = int(bucket_cap_mb * 2 ** 20 / esz)
@@ -117,10 +119,14 @@ class GradReducer:
         self.force_collective = (os.environ.get("PYRECOVER_FORCE_ALLREDUCE") == "1" and dist.is_available()
                                  and dist.is_initialized())
         self.xgmi = None
+        self._end_pending = False  # xgmi + shard: the step barrier waits for the parameter gathers
         if self.backend == "xgmi":
             from .xgmi import XgmiAllReduce
 
-            self.xgmi = XgmiAllReduce(flat, self.ranges, group)
+            # sharded: the engine's reduce-scatter slice r must be owned(b) of rank r; XgmiAllReduce
+            # checks it (parallel/xgmi.py sharded_slices) and reallocates the parameter buffer
+            # IPC-exportable for the parameter all-gather
+            self.xgmi = XgmiAllReduce(flat, self.ranges, group, shard=self.shard)
         # sharded layout: bucket [lo, hi) = W equal chunks of `chunk` elements (a multiple of 64, so
         # every chunk starts 128-B aligned); the shared-tail branches below handle layouts without
         # the relayout's padding (none today)
@@ -130,6 +136,14 @@ class GradReducer:
             self.chunks.append(m // self.world if self.shard else 0)
         self.sparse_bucket = flat.slots[self.sparse_slot].bucket if self.sparse_slot is not None else None
         self._emb_scratch = None
+        if self.xgmi is not None and self.shard:
+            for b in range(len(self.ranges)):
+                if self.owned(b) != [self.xgmi.slices[b][self.rank]]:
+                    raise RuntimeError(f"xgmi sharded optimizer: bucket {b}: owned {self.owned(b)} is not the "
+                                       f"engine's slice {self.xgmi.slices[b][self.rank]}")
+        if self.xgmi is not None and self.sparse_bucket is not None \
+                and self.bucket_slots[self.sparse_bucket] != [self.sparse_slot]:
+            raise RuntimeError("sparse embedding exchange: the embedding slot must be a bucket of its own")
 
     # --- sharded layout ------------------------------------------------------------------
     def owned(self, b: int) -> List[Tuple[int, int]]:
@@ -153,6 +167,10 @@ class GradReducer:
         works (empty when not sharded)."""
         if not self.shard or not self.chunks[b]:
             return []
+        if self.xgmi is not None and not tensors:
+            # the engine pulls the peers' updated chunks from their mapped parameter buffers, behind
+            # the update just enqueued on the current stream (moments stay on the process group)
+            return [self.xgmi.gather(b)]
         lo, _ = self.ranges[b]
         c = self.chunks[b]
         works = []
@@ -171,7 +189,16 @@ class GradReducer:
         e = self.flat.grad.element_size()
         return [(hi - lo) * e for lo, hi in self.ranges]
 
+    def gathers_done(self):
+        """xgmi + shard: the optimizer has issued and waited for the step's parameter all-gathers, so
+        the engine's step barrier can go behind them (the next update of a chunk must not start
+        while a peer still pulls it, nor the next backward while a peer still reduces)."""
+        if self._end_pending:
+            self._end_pending = False
+            self.xgmi.end_step()
+
     def reset(self):
+        self.gathers_done()  # a step without an optimizer update: the barrier still precedes the backward
         self.pending = list(self.counts)
         self.works = [None] * len(self.counts)
         self.next_to_launch = 0
@@ -192,7 +219,11 @@ class GradReducer:
         if self.timer is not None:
             self.timer.ready(b)
         if self.xgmi is not None:
-            work = self.xgmi.launch(b)
+            if b == self.sparse_bucket:
+                slot = self.flat.slots[self.sparse_slot]
+                work = self.xgmi.launch_sparse(b, slot, slot.params[0].shape[0])
+            else:
+                work = self.xgmi.launch(b)
         elif b == self.sparse_bucket:
             work = self._sparse_exchange(b)
             if self.timer is not None:
@@ -233,7 +264,10 @@ class GradReducer:
             self.timer.after_finish()
         self.works = [None] * len(self.counts)
         if self.xgmi is not None:
-            self.xgmi.end_step()
+            if self.shard:
+                self._end_pending = True  # after the parameter gathers: gathers_done()
+            else:
+                self.xgmi.end_step()
 
     def enable_comm_timing(self) -> "CommTimer":
         """Per-step, per-bucket collective timing (bench.py for W > 1)."""

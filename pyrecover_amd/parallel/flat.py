@@ -256,6 +256,23 @@ class FlatParams:
         for s in self.slots:
             s.view = new[s.offset:s.offset + s.numel]
 
+    def rebind_data(self, new: torch.Tensor):
+        """Move the parameter space into ``new`` (same numel/dtype/device; an IPC-exportable
+        allocation for the xGMI parameter all-gather of the sharded optimizer): the values are copied
+        and every ``p.data`` is re-pointed. Like :meth:`relayout`, only before an optimizer binds."""
+        if getattr(self, "layout_frozen", False):
+            raise RuntimeError("rebind_data after an optimizer was bound to the flat buffers")
+        if new.numel() != self.numel or new.dtype != self.data.dtype or new.device != self.data.device:
+            raise ValueError("rebind_data: buffer must match the flat parameter buffer")
+        with torch.no_grad():
+            new.copy_(self.data)
+        self.data = new
+        for p in self.params:
+            o = self.param_offset[id(p)]
+            p.data = new[o:o + p.numel()].view_as(p)
+        if getattr(self, "t_mats", None):
+            self.data_t = None  # re-derived from the new buffer on first use
+
     def zero_grad(self):
         for s in self.slots:
             s.fresh = True

@@ -2,7 +2,7 @@
 
 RCCL's ring moves every byte around the 8 GPUs over one link per direction per ring. On an MI355X
 node every GPU has a direct xGMI link to each of its 7 peers, so this backend works per link
-instead. Default engine (``csrc/dist/xgmi.cpp`` XgmiEngine, native):
+instead. Default engine (``csrc/comm/xgmi.cpp`` XgmiEngine, native):
 
 * reduce-scatter: rank r owns slice r of each bucket; ONE pull-reduce kernel reads slice r from
   every rank's IPC-mapped gradient buffer (the 7 peers' over their xGMI links at once) and sums them
@@ -22,6 +22,14 @@ on its peers' "bucket ready" / "slice reduced" events, and no kernel spins. The 
 guarantees that an event was recorded (for THIS step) before anyone waits on it: every rank
 publishes a per-bucket sequence number in a page of host shared memory right after recording, and
 the worker of a peer polls that word (microseconds). The backward thread never blocks.
+
+Sharded optimizer (``GradReducer(shard=True)``): the reduce-scatter is the pull-reduce alone, and
+after the AdamW update of the owned slice one pull-gather per bucket copies the peers' updated
+slices from their IPC-mapped PARAMETER buffers (:meth:`XgmiAllReduce.gather`; a third per-bucket
+event and sequence word, "updated"). Sparse embedding exchange: the ranks publish their sorted token
+ids in a small IPC-mapped list, and two kernels reduce the union's rows in place in the mapped dense
+gradients, each row by the rank that owns its row range (:meth:`XgmiAllReduce.launch_sparse`,
+``csrc/kernels/comm.hip`` sparse_rows_kernel). The ordering argument is in ``csrc/comm/xgmi.cpp``.
 
 The gradient buffer is reallocated with ``hipMalloc`` so it can be exported with
 ``hipIpcGetMemHandle``. Opt-in: ``GradReducer(..., backend="xgmi")``, ``train.py --allreduce
@@ -60,6 +68,33 @@ def _hidden_ranks(vis) -> List[int]:
     """Ranks whose GPU some rank cannot see; vis[r] = (rank r's device identity, identities rank r sees)."""
     return sorted({r for r, (own, _) in enumerate(vis) for _, seen in vis if own not in seen})
 
+def slice_cuts(lo: int, hi: int, world: int) -> List[int]:
+    """The engine's W + 1 cuts of bucket [lo, hi): rank r reduces [cuts[r], cuts[r + 1]) (8-element =
+    16-B aligned boundaries, the remainder in the last slice)."""
+    n = hi - lo
+    return [lo + ((n * r // world) // 8) * 8 for r in range(world)] + [hi]
+
+
+def sharded_slices(ranges: Sequence[Tuple[int, int]], world: int) -> List[List[Tuple[int, int]]]:
+    """The engine's slices of every bucket for the sharded optimizer, checked: bucket b must be W
+    equal 64-element-aligned chunks (``FlatParams.relayout``'s padded layout), and then slice r is
+    exactly chunk r, ``GradReducer.owned(b)`` of rank r. Anything else is rejected: the optimizer
+    would update elements whose reduced gradient this rank does not hold."""
+    out = []
+    for b, (lo, hi) in enumerate(ranges):
+        n = hi - lo
+        if n <= 0 or n % (64 * world) or lo % 64:
+            raise ValueError(f"xgmi sharded optimizer: bucket {b} [{lo}, {hi}) is not {world} equal 64-element-aligned "
+                             "chunks (an unpadded layout: build the GradReducer before the optimizer)")
+        c = n // world
+        cuts = slice_cuts(lo, hi, world)
+        sl = [(cuts[r], cuts[r + 1]) for r in range(world)]
+        if sl != [(lo + r * c, lo + (r + 1) * c) for r in range(world)]:
+            raise ValueError(f"xgmi sharded optimizer: bucket {b}: the engine's slices {sl} are not the owned chunks")
+        out.append(sl)
+    return out
+
+
 class _Work:
     __slots__ = ("owner", "b", "seq")
 
@@ -71,6 +106,14 @@ class _Work:
     def wait(self):
         """Current stream waits (GPU-side) for the all-reduced bucket."""
         self.owner.eng.wait(self.b, self.seq, torch.cuda.current_stream(self.owner.dev).cuda_stream)
+
+
+class _GatherWork(_Work):
+    __slots__ = ()
+
+    def wait(self):
+        """Current stream waits (GPU-side) for the bucket's parameter all-gather."""
+        self.owner.eng.wait_gather(self.b, self.seq, torch.cuda.current_stream(self.owner.dev).cuda_stream)
 
 
 class _HostSeq:
@@ -136,8 +179,16 @@ class _HostSeq:
 
 
 class XgmiAllReduce:
-    def __init__(self, flat, ranges: Sequence[Tuple[int, int]], group=None):
+    """``shard=True`` (the sharded optimizer): a bucket's launch is the reduce-scatter alone (this
+    rank's slice, :func:`sharded_slices`), and :meth:`gather` pulls the peers' updated parameter slices;
+    for that the flat PARAMETER buffer is reallocated IPC-exportable too and mapped into the peers."""
+
+    def __init__(self, flat, ranges: Sequence[Tuple[int, int]], group=None, shard: bool = False):
         self.C = _ext.native().xgmi
+        self.shard = bool(shard)
+        self.ranges = list(ranges)
+        # sharded: rejected here, before any allocation or collective (every rank raises alike)
+        self.slices = (sharded_slices(self.ranges, dist.get_world_size(group)) if self.shard else None)
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = W = dist.get_world_size(group)
@@ -172,57 +223,51 @@ class XgmiAllReduce:
         buf.copy_(flat.grad)
         flat.rebind_grad(buf)
         self.buf = buf
+        # sharded: the parameter buffer too (FlatParams.relayout just reallocated it, no optimizer is
+        # bound yet), so a peer pulls this rank's updated slice straight from it
+        self.pbuf = None
+        if self.shard:
+            if flat.data.dtype != self.dtype or flat.data.numel() != flat.grad.numel():
+                raise ValueError("xgmi sharded optimizer: parameters and gradients must share dtype and layout")
+            self.pbuf = self.C.ipc_empty(flat.data.numel(), flat.data.dtype, di)
+            flat.rebind_data(self.pbuf)
         # 4) peer buffers (a failed open is reported on every rank)
-        handles: List = [None] * W
-        dist.all_gather_object(handles, self.C.ipc_mem_handle(buf), group=self.hgroup)
-        base = buf.data_ptr()
-        self.peer_base, err = [], None
-        for r in range(W):
-            if r == self.rank:
-                self.peer_base.append(base)
-                continue
-            try:
-                self.peer_base.append(self.C.ipc_open_mem(handles[r], di))
-            except RuntimeError as e:  # noqa: PERF203
-                err = f"rank {self.rank}: ipc_open_mem of rank {r}'s buffer failed: {e}"
-                break
-        errs: List = [None] * W
-        dist.all_gather_object(errs, err, group=self.hgroup)
-        bad = [e for e in errs if e]
-        if bad:
-            raise RuntimeError("xgmi all-reduce cannot map peer gradient buffers (GPU isolation or no "
-                               "dmabuf IPC; HSA_ENABLE_IPC_MODE_LEGACY=0 is required): " + "; ".join(bad))
+        self.peer_base = self._map_peers(buf, "gradient")
+        self.peer_pbase = self._map_peers(self.pbuf, "parameter") if self.shard else []
         # 4) slices (identical on every rank; 8-element = 16-B aligned boundaries)
-        self.ranges = list(ranges)
-        self.slices = []
-        for lo, hi in self.ranges:
-            n = hi - lo
-            cuts = [lo + ((n * r // W) // 8) * 8 for r in range(W)] + [hi]
-            self.slices.append([(cuts[r], cuts[r + 1]) for r in range(W)])
-        # 5) events: per bucket "ready" and "reduced" (interprocess), one per-step "done"
+        if self.slices is None:
+            self.slices = []
+            for lo, hi in self.ranges:
+                cuts = slice_cuts(lo, hi, W)
+                self.slices.append([(cuts[r], cuts[r + 1]) for r in range(W)])
+        # 5) events: per bucket "ready" and "reduced" (and, sharded, "updated"; interprocess), one
+        # per-step "done"
         nb = len(self.ranges)
         self.ev_ready = [self.C.ipc_event_create(di) for _ in range(nb)]
         self.ev_rs = [self.C.ipc_event_create(di) for _ in range(nb)]
+        self.ev_upd = [self.C.ipc_event_create(di) for _ in range(nb)] if self.shard else []
         self.ev_step = self.C.ipc_event_create(di)
         mine = ([self.C.ipc_event_handle(e) for e in self.ev_ready], [self.C.ipc_event_handle(e) for e in self.ev_rs],
-                self.C.ipc_event_handle(self.ev_step))
+                self.C.ipc_event_handle(self.ev_step), [self.C.ipc_event_handle(e) for e in self.ev_upd])
         allh: List = [None] * W
         dist.all_gather_object(allh, mine, group=self.hgroup)
-        self.peer_ready, self.peer_rs, self.peer_step = [], [], []
+        self.peer_ready, self.peer_rs, self.peer_step, self.peer_upd = [], [], [], []
         for r in range(W):
             if r == self.rank:
                 self.peer_ready.append(self.ev_ready)
                 self.peer_rs.append(self.ev_rs)
                 self.peer_step.append(self.ev_step)
+                self.peer_upd.append(self.ev_upd)
             else:
                 self.peer_ready.append([self.C.ipc_event_open(h, di) for h in allh[r][0]])
                 self.peer_rs.append([self.C.ipc_event_open(h, di) for h in allh[r][1]])
                 self.peer_step.append(self.C.ipc_event_open(allh[r][2], di))
-        # 6) host sequence words: [ready b | reduced b | step]
+                self.peer_upd.append([self.C.ipc_event_open(h, di) for h in allh[r][3]])
+        # 6) host sequence words: [ready b | reduced b | updated b | step]
         self.nb = nb
         self.seq = 1  # current step's sequence number (published values start at 1)
-        self.hseq = _HostSeq(self.rank, W, 2 * nb + 1, self.hgroup)
-        # the native engine (csrc/dist/xgmi.cpp XgmiEngine): one comm stream, one pull-reduce kernel
+        self.hseq = _HostSeq(self.rank, W, self.C.XgmiEngine.words_per_rank(nb), self.hgroup)
+        # the native engine (csrc/comm/xgmi.cpp XgmiEngine): one comm stream, one pull-reduce kernel
         # reading every peer's slice over xGMI and one pull-gather kernel per bucket, scheduled by a
         # C++ worker thread
         code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[self.dtype]
@@ -231,14 +276,79 @@ class XgmiAllReduce:
             di, self.rank, W, code, self.esz, list(self.peer_base), cuts, self.hseq.address(),
             list(self.ev_ready), list(self.ev_rs), self.ev_step,
             [e for r in range(W) for e in self.peer_ready[r]], [e for r in range(W) for e in self.peer_rs[r]],
-            list(self.peer_step))
+            list(self.peer_step), list(self.peer_pbase), list(self.ev_upd),
+            [e for r in range(W) for e in self.peer_upd[r]] if self.shard else [])
+        self.ids_buf = None  # sparse exchange: this rank's published id list (allocated at first use)
         dist.barrier(group=self.hgroup)
+
+    def _map_peers(self, buf: torch.Tensor, what: str) -> List[int]:
+        """Exchange ``buf``'s IPC handle and map every peer's buffer; a failed open is reported on
+        every rank. Returns the W base addresses (this rank's own at index rank)."""
+        W, di = self.world, self.dev.index
+        handles: List = [None] * W
+        dist.all_gather_object(handles, self.C.ipc_mem_handle(buf), group=self.hgroup)
+        out, err = [], None
+        for r in range(W):
+            if r == self.rank:
+                out.append(buf.data_ptr())
+                continue
+            try:
+                out.append(self.C.ipc_open_mem(handles[r], di))
+            except RuntimeError as e:  # noqa: PERF203
+                err = f"rank {self.rank}: ipc_open_mem of rank {r}'s buffer failed: {e}"
+                break
+        errs: List = [None] * W
+        dist.all_gather_object(errs, err, group=self.hgroup)
+        bad = [e for e in errs if e]
+        if bad:
+            raise RuntimeError(f"xgmi all-reduce cannot map peer {what} buffers (GPU isolation or no "
+                               "dmabuf IPC; HSA_ENABLE_IPC_MODE_LEGACY=0 is required): " + "; ".join(bad))
+        return out
 
     # --- backward thread -----------------------------------------------------------------
     def launch(self, b: int) -> _Work:
         w = _Work(self, b)
         w.seq = self.eng.launch(b, torch.cuda.current_stream(self.dev).cuda_stream)
         return w
+
+    def gather(self, b: int) -> _GatherWork:
+        """Sharded: bucket b's owned parameter slice was updated on the current stream; pull the
+        peers' updated slices behind it (one pull-gather on the comm stream)."""
+        w = _GatherWork(self, b)
+        w.seq = self.eng.gather(b, torch.cuda.current_stream(self.dev).cuda_stream)
+        return w
+
+    def launch_sparse(self, b: int, slot, vocab: int) -> _Work:
+        """Bucket b holds only ``slot``, a [vocab, D] embedding gradient whose non-zero rows are those
+        of ``slot.sparse_ids``: publish the ids, sorted (fixed size, duplicates kept, no host sync for
+        a count), in an IPC-mapped list and reduce the union's rows in place (XgmiEngine, sparse
+        bucket). The list is allocated, and mapped into the peers, at the first step: a collective,
+        every rank gets here in the same backward. Later steps may bring fewer ids (the tail is filled
+        with ``vocab``, which the kernel skips as out of range), never more."""
+        ids = getattr(slot, "sparse_ids", None)
+        if ids is None:
+            raise RuntimeError("sparse embedding exchange: the embedding backward recorded no token ids")
+        s, _ = torch.sort(ids.reshape(-1).to(torch.int64))
+        n = s.numel()
+        if self.ids_buf is None:
+            ns: List = [None] * self.world
+            dist.all_gather_object(ns, n, group=self.hgroup)
+            if len(set(ns)) != 1 or n == 0:
+                raise RuntimeError(f"sparse embedding exchange: the ranks' token counts per step differ: {ns}")
+            D = slot.numel // vocab
+            if D * vocab != slot.numel or D % 8:
+                raise ValueError(f"sparse embedding exchange on xgmi: the embedding width {D} must be a multiple of 8")
+            self.ids_buf = self.C.ipc_empty(n, torch.int64, self.dev.index)
+            self.peer_ids = self._map_peers(self.ids_buf, "token id")
+            self.eng.set_sparse(b, slot.offset, vocab, D, n, list(self.peer_ids))
+        cap = self.ids_buf.numel()
+        if n > cap:
+            raise RuntimeError(f"sparse embedding exchange: {n} token ids this step, the list was sized for {cap}")
+        self.ids_buf[:n].copy_(s)
+        if n < cap:
+            self.ids_buf[n:].fill_(vocab)
+        slot.sparse_ids = None
+        return self.launch(b)
 
     def end_step(self):
         """After every bucket of the step was waited on: no rank may overwrite its gradient

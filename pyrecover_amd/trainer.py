@@ -256,8 +256,9 @@ def train(args):
     if is_dist or overlap:
         reducer = GradReducer(flat, bucket_cap_mb=bucket_mb, backend=args.allreduce, shard=shard,
                               sparse_slot=flat.slot(model.tok_embeddings.weight).index if sparse_emb else None)
+        comm_name = "xGMI engine" if reducer.backend == "xgmi" else "RCCL"
         log_rank0(f"Gradient buckets: {reducer.num_buckets}, {sum(reducer.bucket_bytes()) / 2**30:.2f} GiB"
-                  f"{(' (RCCL reduce-scatter + all-gather, sharded optimizer)' if shard else ' (RCCL all-reduce)') if is_dist else ''}"
+                  f"{(f' ({comm_name} reduce-scatter + all-gather, sharded optimizer)' if shard else f' ({comm_name} all-reduce)') if is_dist else ''}"
                   f"{', sparse embedding-gradient exchange' if sparse_emb and is_dist else ''}")
         if reducer.force_collective and not is_dist:
             log_rank0("Bucket collectives forced on in a 1-rank "
