@@ -106,6 +106,7 @@ at::Tensor rmsnorm_bwd(const at::Tensor& dy, const at::Tensor& h, const at::Tens
               "rmsnorm_bwd: shape mismatch");
   TORCH_CHECK(dw.scalar_type() == h.scalar_type() && dy.scalar_type() == h.scalar_type(), "rmsnorm_bwd: dtype");
   TORCH_CHECK(rstd.scalar_type() == at::kFloat && rstd.is_contiguous(), "rmsnorm_bwd: rstd must be contiguous fp32");
+  TORCH_CHECK(D % 8 == 0 && D <= 8192, "rmsnorm_bwd: D must be a multiple of 8 and <= 8192");
   same_dev(dy, h, "h");
   same_dev(dy, w, "w");
   same_dev(dy, rstd, "rstd");
@@ -169,6 +170,7 @@ at::Tensor layernorm_bwd(const at::Tensor& dy, const at::Tensor& h, const at::Te
               mean.numel() == rows, "layernorm_bwd: shapes");
   TORCH_CHECK(dwb.scalar_type() == h.scalar_type() && dy.scalar_type() == h.scalar_type() &&
               rstd.scalar_type() == at::kFloat && mean.scalar_type() == at::kFloat, "layernorm_bwd: dtypes");
+  TORCH_CHECK(D % 8 == 0 && D <= 8192, "layernorm_bwd: D must be a multiple of 8 and <= 8192");
   for (const at::Tensor& t : {h, w, mean, rstd, dwb}) same_dev(dy, t, "layernorm operand");
   if (dres.has_value()) {
     TORCH_CHECK(dres->sizes() == h.sizes() && dres->is_contiguous() && dres->scalar_type() == h.scalar_type(),
@@ -343,11 +345,19 @@ void embedding_bwd(const at::Tensor& ids, const at::Tensor& dout, at::Tensor dW,
         "embedding_bwd");
 }
 
+// The kernels read rows in 8-element vectors from the row start: a V that is not a multiple of 8 must
+// be a [:, :V] view of a buffer whose rows are padded to one.
+void check_xent_stride(const at::Tensor& logits) {
+  TORCH_CHECK(logits.stride(0) % 8 == 0, "xent: the logits row stride must be a multiple of 8 elements (row stride % 8 "
+              "== 0), got ", logits.stride(0), " for V = ", logits.size(1), "; pass a [:, :V] view of a padded buffer");
+}
+
 // logits [T, V] (row stride ld), labels [T] -> (lse [T], loss_row [T], stats [2] = {mean loss, n_valid})
 std::vector<at::Tensor> xent_fwd(const at::Tensor& logits, const at::Tensor& labels, int64_t ignore_index) {
   const Range range_("pyrecover::xent_fwd");
   check_dev(logits, "logits");
   check_row_major(logits, "logits");
+  check_xent_stride(logits);
   TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == logits.size(0),
               "xent: labels must be contiguous int64 [T]");
   same_dev(logits, labels, "labels");
@@ -367,6 +377,7 @@ void xent_bwd_(at::Tensor logits, const at::Tensor& labels, const at::Tensor& ls
   const Range range_("pyrecover::xent_bwd");
   check_dev(logits, "logits");
   check_row_major(logits, "logits");
+  check_xent_stride(logits);
   TORCH_CHECK(grad_out.scalar_type() == at::kFloat && grad_out.numel() == 1 && grad_out.is_cuda(),
               "xent_bwd: grad_out must be a 1-element fp32 GPU tensor");
   TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == logits.size(0),

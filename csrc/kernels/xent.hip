@@ -1,5 +1,7 @@
 // Fused causal-LM cross-entropy over bf16/fp16/fp32 logits (reference train.py:263-266:
 // `cross_entropy(logits.float(), labels, reduction="sum") / labels.ne(-100).sum()`).
+// A label outside [0, V) is treated exactly like `ignore_index` by all three kernels (label_valid):
+// loss 0, not counted in n_valid, zero gradient row.
 //
 // Forward: one 256-thread block per row, a single streaming pass with an online
 // (max, sum-exp) pair per lane -> per-row log-sum-exp and loss, no fp32 copy of the logits.
@@ -10,6 +12,10 @@
 #include "common.h"
 
 namespace pra {
+
+__device__ __forceinline__ bool label_valid(long lab, long V, long ignore_index) {
+  return lab != ignore_index && lab >= 0 && lab < V;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ labels,
@@ -58,19 +64,19 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const T* __restrict__ log
     const float lse = M + __logf(S);
     lse_out[row] = lse;
     const long lab = labels[row];
-    loss_row[row] = (lab == ignore_index || lab < 0 || lab >= V) ? 0.f : lse - to_f<T>(x[lab]);
+    loss_row[row] = label_valid(lab, V, ignore_index) ? lse - to_f<T>(x[lab]) : 0.f;
   }
 }
 
 // out[0] = sum(loss_row) / n_valid ; out[1] = n_valid (as float). One block, fixed order.
 __global__ __launch_bounds__(256) void xent_reduce_kernel(const float* __restrict__ loss_row,
                                                           const int64_t* __restrict__ labels, float* __restrict__ out,
-                                                          long T, long ignore_index) {
+                                                          long T, long V, long ignore_index) {
   __shared__ float red[4];
   float s = 0.f, n = 0.f;
   for (long i = threadIdx.x; i < T; i += 256) {
     s += loss_row[i];
-    n += (labels[i] != ignore_index) ? 1.f : 0.f;
+    n += label_valid(labels[i], V, ignore_index) ? 1.f : 0.f;
   }
   s = block_sum<4>(s, red);
   n = block_sum<4>(n, red);
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(T* __restrict__ logits, c
   const long row = blockIdx.x;
   T* x = logits + row * ld;
   const long lab = labels[row];
-  const bool ign = (lab == ignore_index);
+  const bool ign = !label_valid(lab, V, ignore_index);
   const float scale = ign ? 0.f : grad_out[0] / stats[1];
   const float l = lse[row];
   const long V8 = (V / 8) * 8;
@@ -116,7 +122,7 @@ hipError_t pra_xent_fwd(int dtype, const void* logits, const int64_t* labels, fl
   PRA_DISPATCH_FLOAT(dtype, LT,
                      hipLaunchKernelGGL((pra::xent_fwd_kernel<LT>), dim3(T), dim3(256), 0, s, (const LT*)logits,
                                         labels, lse, loss_row, V, ld, ignore_index));
-  hipLaunchKernelGGL(pra::xent_reduce_kernel, dim3(1), dim3(256), 0, s, loss_row, labels, stats, T, ignore_index);
+  hipLaunchKernelGGL(pra::xent_reduce_kernel, dim3(1), dim3(256), 0, s, loss_row, labels, stats, T, V, ignore_index);
   return hipGetLastError();
 }
 
