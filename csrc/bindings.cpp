@@ -395,9 +395,18 @@ void xent_bwd_(at::Tensor logits, const at::Tensor& labels, const at::Tensor& ls
         "xent_bwd");
 }
 
+// The AdamW kernels' optional skip flag: int32[>=1] on p's device (non-zero: the launch does nothing).
+static const int* skip_flag(const at::Tensor& p, const c10::optional<at::Tensor>& skip_dev) {
+  if (!skip_dev.has_value()) return nullptr;
+  TORCH_CHECK(skip_dev->scalar_type() == at::kInt && skip_dev->numel() >= 1, "adamw: skip_dev int32");
+  same_dev(p, *skip_dev, "skip_dev");
+  return skip_dev->data_ptr<int>();
+}
+
 void adamw_flat_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, double lr, double b1, double b2,
                  double eps, double wd, double bc1, double bc2_sqrt, double gscale,
-                 const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast) {
+                 const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
+    const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_flat");
   check_dev(p, "p");
   TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), "adamw: contiguous");
@@ -419,16 +428,18 @@ void adamw_flat_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, 
     same_dev(p, *hyper_dev, "hyper_dev");
     hyd = hyper_dev->data_ptr<double>();
   }
+  const int* skd = skip_flag(p, skip_dev);
   check(pra_adamw_flat(dt(p), dt(m), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1,
                        b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd,
-                       hyd, fast ? 1 : 0, stream_of(p)),
+                       hyd, fast ? 1 : 0, skd, stream_of(p)),
         "adamw_flat");
 }
 
 // fp32-master AdamW: pm, m, v fp32; p (16-bit) <- round(pm); g has p's dtype.
 void adamw_master_(at::Tensor p, at::Tensor pm, const at::Tensor& g, at::Tensor m, at::Tensor v, double lr, double b1,
                    double b2, double eps, double wd, double bc1, double bc2_sqrt, double gscale,
-                   const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast) {
+                   const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
+    const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_master");
   check_dev(p, "p");
   TORCH_CHECK(p.is_contiguous() && pm.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
@@ -452,16 +463,18 @@ void adamw_master_(at::Tensor p, at::Tensor pm, const at::Tensor& g, at::Tensor 
     same_dev(p, *hyper_dev, "hyper_dev");
     hyd = hyper_dev->data_ptr<double>();
   }
+  const int* skd = skip_flag(p, skip_dev);
   check(pra_adamw_master(dt(p), p.data_ptr(), pm.data_ptr<float>(), g.data_ptr(), m.data_ptr<float>(),
                          v.data_ptr<float>(), p.numel(), lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd,
-                         fast ? 1 : 0, stream_of(p)),
+                         fast ? 1 : 0, skd, stream_of(p)),
         "adamw_master");
 }
 
 // AdamW of one row-major weight matrix p [rows, cols] that also writes pt = p^T [cols, rows].
 void adamw_t_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor pt, double lr, double b1,
               double b2, double eps, double wd, double bc1, double bc2_sqrt, double gscale,
-              const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast) {
+              const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
+    const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_t");
   check_dev(p, "p");
   TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && g.sizes() == p.sizes() && m.sizes() == p.sizes() &&
@@ -490,8 +503,10 @@ void adamw_t_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at:
     same_dev(p, *hyper_dev, "hyper_dev");
     hyd = hyper_dev->data_ptr<double>();
   }
+  const int* skd = skip_flag(p, skip_dev);
   check(pra_adamw_t(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)rows,
-                    (int)cols, lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, stream_of(p)),
+                    (int)cols, lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd,
+                    stream_of(p)),
         "adamw_t");
 }
 
@@ -666,6 +681,45 @@ at::Tensor grad_norm(const at::Tensor& x, double max_norm, double pre_scale) {
                       (float)pre_scale, stream_of(x)),
         "grad_norm");
   return out;
+}
+
+// Loss-scale / non-finite guard step (optim.hip guard_finish_kernel): the sum of squares of x, or the
+// squared norm sq (fp64[1], sharded optimizer), decides the skip flag, the scale state, the gradient
+// multiplier out[1] and the bias corrections hyper[1:3]. state int32[8], out fp32[2], hyper fp64[3].
+void guard_step_(const c10::optional<at::Tensor>& x, const c10::optional<at::Tensor>& sq, at::Tensor state,
+                 at::Tensor out, at::Tensor hyper, double max_norm, double pre_scale, bool dynamic, int64_t interval,
+                 double b1, double b2) {
+  const Range range_("pyrecover::guard_step");
+  check_dev(state, "state");
+  TORCH_CHECK(x.has_value() != sq.has_value(), "guard_step: exactly one of x and sq");
+  TORCH_CHECK(state.scalar_type() == at::kInt && state.numel() >= 8 && state.is_contiguous(), "guard_step: state int32[8]");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.numel() >= 2 && out.is_contiguous(), "guard_step: out fp32[2]");
+  TORCH_CHECK(hyper.scalar_type() == at::kDouble && hyper.numel() >= 3 && hyper.is_contiguous(),
+              "guard_step: hyper fp64[3]");
+  TORCH_CHECK(interval >= 1 && interval <= INT32_MAX, "guard_step: interval");
+  same_dev(state, out, "out");
+  same_dev(state, hyper, "hyper");
+  const c10::DeviceGuard guard(state.device());
+  const void* xp = nullptr;
+  const double* sqp = nullptr;
+  int xdt = 0;
+  int64_t n = 0;
+  if (x.has_value()) {
+    TORCH_CHECK(x->is_contiguous(), "guard_step: contiguous");
+    same_dev(state, *x, "x");
+    xp = x->data_ptr();
+    xdt = dt(*x);
+    n = x->numel();
+  } else {
+    TORCH_CHECK(sq->scalar_type() == at::kDouble && sq->numel() >= 1, "guard_step: sq fp64[1]");
+    same_dev(state, *sq, "sq");
+    sqp = sq->data_ptr<double>();
+  }
+  at::Tensor ws = at::empty({pra_sumsq_partials()}, state.options().dtype(at::kFloat));
+  check(pra_guard_step(xdt, xp, n, sqp, ws.data_ptr<float>(), state.data_ptr<int>(), out.data_ptr<float>(),
+                       hyper.data_ptr<double>(), (float)max_norm, (float)pre_scale, dynamic ? 1 : 0, (int)interval, b1,
+                       b2, stream_of(state)),
+        "guard_step");
 }
 
 // replica checksum of a contiguous buffer: {fp64 sum of its elements, 64-bit word hash (int64 bits)}
@@ -905,16 +959,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("adamw_flat_", &adamw_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
         py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false);
+        py::arg("fast") = false, py::arg("skip_dev") = py::none());
   m.def("adamw_t_", &adamw_t_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("pt"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
         py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false);
+        py::arg("fast") = false, py::arg("skip_dev") = py::none());
   m.def("adamw_master_", &adamw_master_, py::arg("p"), py::arg("pm"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
         py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false);
+        py::arg("fast") = false, py::arg("skip_dev") = py::none());
   m.def("grad_norm", &grad_norm);
+  m.def("guard_step_", &guard_step_, py::arg("x"), py::arg("sq"), py::arg("state"), py::arg("out"), py::arg("hyper"),
+        py::arg("max_norm"), py::arg("pre_scale"), py::arg("dynamic"), py::arg("interval"), py::arg("b1"),
+        py::arg("b2"));
   m.def("checksum", &checksum);
   m.def("wgrad_mm_", &wgrad_mm_);
   m.def("wgrad_mm_exp_", &wgrad_mm_exp_);

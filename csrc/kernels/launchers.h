@@ -62,14 +62,21 @@ hipError_t pra_xent_bwd(int dtype, void* logits, const int64_t* labels, const fl
 
 hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n, double lr,
                           double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s);
+                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+    hipStream_t s);
 // fp32-master AdamW: updates pm / m / v (fp32) and writes p = round(pm) (16-bit params)
 hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n, double lr,
                             double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                            const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s);
+                            const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+    hipStream_t s);
 int pra_sumsq_partials();
 hipError_t pra_grad_norm(int dtype, const void* x, long n, float* ws, float* out, float max_norm, float pre_scale,
                          hipStream_t s);
+// loss-scale / non-finite guard: grad_norm's reduction (or sq_dev, fp64[1]) + the skip decision and scale
+// state machine on the device (optim.hip guard_finish_kernel documents state / out / hyper)
+hipError_t pra_guard_step(int dtype, const void* x, long n, const double* sq_dev, float* ws, int* state, float* out,
+                          double* hyper, float max_norm, float pre_scale, int dynamic, int interval, double b1,
+                          double b2, hipStream_t s);
 
 // dst <- src, nbytes, device memory (16-B vector path when both are 16-B aligned)
 hipError_t pra_copy_d2d(void* dst, const void* src, long nbytes, hipStream_t s);
@@ -86,7 +93,8 @@ hipError_t pra_sparse_rows(int dtype, int phase, void* const* grads, const int64
 
 hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
                        double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                       const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s);
+                       const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+    hipStream_t s);
 
 hipError_t pra_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
                         int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal,

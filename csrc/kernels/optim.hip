@@ -17,7 +17,10 @@
 // `gscale` pre-multiplies the gradient (1/world_size after a SUM all-reduce, and/or a
 // clip coefficient read from device memory when `gscale_dev` is non-null). `hyper_dev`, when
 // non-null, supplies {lr, bc1, bc2_sqrt} from device memory so a captured HIP graph of the
-// training step replays with the current learning rate and bias corrections.
+// training step replays with the current learning rate and bias corrections. `skip_dev`, when
+// non-null and non-zero in device memory, makes the launch a no-op (train.py --loss-scale: the step's
+// gradient is not finite, guard_finish_kernel below); a zero multiplier alone would still decay the
+// weights and the moments. A null `skip_dev` is the unguarded path.
 #include "common.h"
 
 namespace pra {
@@ -147,7 +150,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(P* __restrict__ p, const P* 
                                                     S* __restrict__ v, long n, double lr, double b1, double b2,
                                                     double eps, double wd, double bc1, double bc2_sqrt, float gscale,
                                                     const float* __restrict__ gscale_dev,
-                                                    const double* __restrict__ hyper_dev) {
+                                                    const double* __restrict__ hyper_dev,
+                                                    const int* __restrict__ skip_dev) {
+  if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
   const long n8 = n / 8;
@@ -181,7 +186,9 @@ __global__ __launch_bounds__(256) void adamw16_kernel(P* __restrict__ p, const P
                                                       P* __restrict__ v, long n, double lr, double b1, double b2,
                                                       double eps, double wd, double bc1, double bc2_sqrt, float gscale,
                                                       const float* __restrict__ gscale_dev,
-                                                      const double* __restrict__ hyper_dev) {
+                                                      const double* __restrict__ hyper_dev,
+                                                    const int* __restrict__ skip_dev) {
+  if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
   const long n8 = n / 8, stride = (long)gridDim.x * 256 * U;
@@ -228,7 +235,9 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(P* __restrict__ p, fl
                                                            double b2, double eps, double wd, double bc1,
                                                            double bc2_sqrt, float gscale,
                                                            const float* __restrict__ gscale_dev,
-                                                           const double* __restrict__ hyper_dev) {
+                                                           const double* __restrict__ hyper_dev,
+                                                    const int* __restrict__ skip_dev) {
+  if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
   const long n8 = n / 8;
@@ -267,10 +276,12 @@ __global__ __launch_bounds__(256) void adamw_t_kernel(P* __restrict__ p, const P
                                                       double lr, double b1, double b2, double eps, double wd,
                                                       double bc1, double bc2_sqrt, float gscale,
                                                       const float* __restrict__ gscale_dev,
-                                                      const double* __restrict__ hyper_dev) {
+                                                      const double* __restrict__ hyper_dev,
+                                                      const int* __restrict__ skip_dev) {
   constexpr int CH = TILE / 8;            // 8-element chunks per tile row
   constexpr int PASSES = TILE * CH / 256;  // chunks per thread
   __shared__ uint16_t tile[TILE][TILE + 8];
+  if (skip_dev && *skip_dev != 0) return;  // block-uniform, before the barrier below
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
   const long r0 = (long)blockIdx.y * TILE, c0 = (long)blockIdx.x * TILE;
@@ -337,6 +348,72 @@ __global__ __launch_bounds__(256) void norm_finish_kernel(const float* __restric
   }
 }
 
+// Loss-scale / non-finite guard (train.py --loss-scale): the finish of the gradient-norm reduction
+// that also decides, on the device, whether this step's update runs, and keeps the scale state.
+//
+// Guard state, int32[8] in device memory (optim/adamw.py LossScaleGuard):
+//   [0] loss scale s (fp32 bits)           [1] growth tracker (applied steps since the last change of s)
+//   [2] found: 1 when this step's gradient is not finite -- the AdamW kernels' skip_dev
+//   [3] applied steps (AdamW's bias-correction step count)
+//   [4] skipped steps, total               [5] consecutive skipped steps        [6], [7] reserved
+// Input: the fp32 partials of sumsq_kernel over the reduced, scaled gradient, summed in fixed order, or
+// (sq_dev non-null: sharded optimizer) its squared norm summed over the ranks in fp64.
+//   found = !isfinite(sum of squares)
+//   found:  out = {norm, 0}; skipped += 1, consecutive += 1; dynamic: s *= 0.5, tracker = 0
+//   else:   out = {norm, clip / s}; applied += 1, consecutive = 0; hyper[1] = 1 - b1^applied,
+//           hyper[2] = sqrt(1 - b2^applied) (fp64, as torch's fused AdamW computes them from its device
+//           step count); dynamic: tracker += 1, and at tracker == interval s *= 2, tracker = 0
+// norm = sqrt(sum) * pre_scale / s is the unscaled gradient norm, clip = min(1, max_norm / (norm + 1e-6))
+// (1 when max_norm <= 0). The tests are on the exponent bits, so no floating-point compile flag can
+// fold them away; this file is built without finite-math flags (NaN and inf must survive the sums).
+__global__ __launch_bounds__(256) void guard_finish_kernel(const float* __restrict__ partial, int np,
+                                                           const double* __restrict__ sq_dev, int* __restrict__ state,
+                                                           float* __restrict__ out, double* __restrict__ hyper,
+                                                           float max_norm, float pre_scale, int dynamic, int interval,
+                                                           double b1, double b2) {
+  __shared__ float red[4];
+  float s = 0.f;
+  if (!sq_dev) {
+    for (int i = threadIdx.x; i < np; i += 256) s += partial[i];
+    s = block_sum<4>(s, red);
+  }
+  if (threadIdx.x == 0) {
+    const double sq = sq_dev ? sq_dev[0] : (double)s;
+    const bool found = ((unsigned long long)__double_as_longlong(sq) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+    float scale = __int_as_float(state[0]);
+    const float norm = (float)(sqrt(sq) * (double)pre_scale / (double)scale);
+    out[0] = norm;
+    if (found) {
+      out[1] = 0.f;
+      state[2] = 1;
+      state[4] += 1;
+      state[5] += 1;
+      if (dynamic) {
+        state[0] = __float_as_int(scale * 0.5f);
+        state[1] = 0;
+      }
+    } else {
+      const float clip = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+      out[1] = clip / scale;
+      const int applied = state[3] + 1;
+      state[2] = 0;
+      state[3] = applied;
+      state[5] = 0;
+      hyper[1] = 1.0 - pow(b1, (double)applied);
+      hyper[2] = sqrt(1.0 - pow(b2, (double)applied));
+      if (dynamic) {
+        const int tracker = state[1] + 1;
+        if (tracker == interval) {
+          state[0] = __float_as_int(scale * 2.f);
+          state[1] = 0;
+        } else {
+          state[1] = tracker;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace pra
 
 extern "C" {
@@ -344,7 +421,7 @@ extern "C" {
 // pdtype: param/grad dtype; sdtype: moment dtype
 hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n, double lr,
                           double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s) {
+                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
   long blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
@@ -359,12 +436,12 @@ hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* 
       PRA_DISPATCH_16BIT(pdtype, T,
                          hipLaunchKernelGGL((pra::adamw16_kernel<T, true, 2>), dim3(nb), dim3(256), 0, s, (T*)p,
                                             (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                            gscale_dev, hyper_dev));
+                                            gscale_dev, hyper_dev, skip_dev));
     } else {
       PRA_DISPATCH_16BIT(pdtype, T,
                          hipLaunchKernelGGL((pra::adamw16_kernel<T, false, 2>), dim3(nb), dim3(256), 0, s,
                                             (T*)p, (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt,
-                                            gscale, gscale_dev, hyper_dev));
+                                            gscale, gscale_dev, hyper_dev, skip_dev));
     }
     return hipGetLastError();
   }
@@ -372,11 +449,11 @@ hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* 
   if (fast) {
     hipLaunchKernelGGL((pra::adamw_kernel<float, float, true>), dim3(blocks), dim3(256), 0, s, (float*)p,
                        (const float*)g, (float*)m, (float*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev,
-                       hyper_dev);
+                       hyper_dev, skip_dev);
   } else {
     hipLaunchKernelGGL((pra::adamw_kernel<float, float, false>), dim3(blocks), dim3(256), 0, s, (float*)p,
                        (const float*)g, (float*)m, (float*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev,
-                       hyper_dev);
+                       hyper_dev, skip_dev);
   }
   return hipGetLastError();
 }
@@ -386,7 +463,7 @@ hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* 
 // non-temporal (Llama-3-8B B1 with shadows -1.03%, 7B B16 within noise: profiles/r6/adamw/).
 hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
                        double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                       const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s) {
+                       const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
   if (rows % 64 || cols % 64 || rows <= 0 || cols <= 0) return hipErrorInvalidValue;
   // (A strip kernel walking 4 tiles per block was faster in isolation, 22.7 -> 21.3 ms per 7B step,
   // but slower overlapped with the backward GEMMs on the side stream: 1074.5 vs 1069.6 ms/step,
@@ -397,7 +474,7 @@ hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void
   PRA_DISPATCH_16BIT(dtype, T,                                                                                  \
                      hipLaunchKernelGGL((pra::adamw_t_kernel<T, FASTV, TILEV, true>), grid, dim3(256), 0, s,    \
                                         (T*)p, (const T*)g, (T*)m, (T*)v, (T*)pt, rows, cols, lr, b1, b2, eps,   \
-                                        wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev))
+                                        wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev))
   if (tile == 128 && fast) {
     PRA_ADAMW_T(true, 128);
   } else if (tile == 128) {
@@ -413,7 +490,7 @@ hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void
 
 hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n, double lr,
                             double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                            const float* gscale_dev, const double* hyper_dev, int fast, hipStream_t s) {
+                            const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
   long blocks = (n / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
@@ -421,12 +498,12 @@ hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float
     PRA_DISPATCH_16BIT(pdtype, T,
                        hipLaunchKernelGGL((pra::adamw_master_kernel<T, true>), dim3(blocks), dim3(256), 0, s, (T*)p,
                                           pm, (const T*)g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev));
+                                          gscale_dev, hyper_dev, skip_dev));
   } else {
     PRA_DISPATCH_16BIT(pdtype, T,
                        hipLaunchKernelGGL((pra::adamw_master_kernel<T, false>), dim3(blocks), dim3(256), 0, s, (T*)p,
                                           pm, (const T*)g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev));
+                                          gscale_dev, hyper_dev, skip_dev));
   }
   return hipGetLastError();
 }
@@ -440,6 +517,24 @@ hipError_t pra_grad_norm(int dtype, const void* x, long n, float* ws, float* out
   PRA_DISPATCH_FLOAT(dtype, T,
                      hipLaunchKernelGGL((pra::sumsq_kernel<T>), dim3(np), dim3(256), 0, s, (const T*)x, n, ws));
   hipLaunchKernelGGL(pra::norm_finish_kernel, dim3(1), dim3(256), 0, s, ws, np, out, max_norm, pre_scale);
+  return hipGetLastError();
+}
+
+// Guard step (guard_finish_kernel): x non-null: sum of squares of x[0:n] through ws, else the squared
+// norm comes from sq_dev (fp64[1]). state: int32[8], out: float[2] = {unscaled norm, gradient
+// multiplier}, hyper: fp64[3] (the AdamW kernels' hyper_dev; [1] and [2] are written).
+hipError_t pra_guard_step(int dtype, const void* x, long n, const double* sq_dev, float* ws, int* state, float* out,
+                          double* hyper, float max_norm, float pre_scale, int dynamic, int interval, double b1,
+                          double b2, hipStream_t s) {
+  const int np = 1024;
+  if (x) {
+    PRA_DISPATCH_FLOAT(dtype, T,
+                       hipLaunchKernelGGL((pra::sumsq_kernel<T>), dim3(np), dim3(256), 0, s, (const T*)x, n, ws));
+  } else if (!sq_dev) {
+    return hipErrorInvalidValue;
+  }
+  hipLaunchKernelGGL(pra::guard_finish_kernel, dim3(1), dim3(256), 0, s, ws, np, x ? nullptr : sq_dev, state, out,
+                     hyper, max_norm, pre_scale, dynamic, interval, b1, b2);
   return hipGetLastError();
 }
 

@@ -185,10 +185,25 @@ def build_state(model, optimizer, lr_scheduler=None, sampler=None, step: int = 0
         ps["world_size"] = torch.distributed.get_world_size()
     if rng_per_rank is not None:
         ps["rng_per_rank"] = rng_per_rank
+    guard = getattr(optimizer, "guard", None)
+    if guard is not None:
+        # --loss-scale: scale, growth tracker, applied and skipped step counts. Kept here, not in the
+        # optimizer state, whose keys stay torch.optim.AdamW's (the reference's)
+        ps["loss_scale"] = guard.state_dict()
     if extra:
         ps.update(extra)
     state["pyrecover_state"] = ps
     return state
+
+
+def restore_loss_scale(optimizer, ps: Optional[Dict[str, Any]]):
+    """Restore the --loss-scale state from a checkpoint's ``pyrecover_state``. A checkpoint without
+    one (written with --loss-scale off, or the reference's) leaves the command line's initial scale;
+    the applied-step count then is the optimizer's loaded step."""
+    guard = getattr(optimizer, "guard", None)
+    sd = (ps or {}).get("loss_scale")
+    if guard is not None and sd:
+        guard.load_state_dict({k: (v.item() if isinstance(v, torch.Tensor) else v) for k, v in sd.items()})
 
 
 # ------------------------------------------------------------------------------------------

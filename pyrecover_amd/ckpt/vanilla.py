@@ -102,6 +102,7 @@ def load_state_into(model, optimizer, lr_scheduler, sampler, ckpt) -> Tuple[int,
         raise RuntimeError(f"checkpoint/model key mismatch: missing={missing[:5]} unexpected={unexpected[:5]}")
     if optimizer is not None and "optimizer" in ckpt:
         optimizer.load_state_dict(ckpt["optimizer"])
+        core.restore_loss_scale(optimizer, ckpt.get("pyrecover_state"))
     if lr_scheduler is not None and "lr_scheduler" in ckpt:
         sd = dict(ckpt["lr_scheduler"])
         if hasattr(lr_scheduler, "lr_lambdas"):

@@ -123,6 +123,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="snapshot to pinned host memory and write in the background while training continues")
     p.add_argument("--no-fsync", action="store_true", help="skip fsync of checkpoint files")
     p.add_argument("--clip-grad", action="store_true", help="enable gradient clipping at --grad-max-norm")
+    p.add_argument("--loss-scale", type=_loss_scale, default="off", metavar="off|dynamic|<float>",
+                   help="multiply the loss by a scale before the backward and skip, on the device, any step whose "
+                        "reduced gradient is not finite. dynamic: start at --loss-scale-init, halve on a skipped "
+                        "step, double after --loss-scale-growth-interval applied steps in a row; <float>: a fixed "
+                        "scale (1: the plain non-finite guard for bf16). AdamW then runs after the backward")
+    p.add_argument("--loss-scale-init", type=float, default=65536.0, help="initial scale of --loss-scale dynamic")
+    p.add_argument("--loss-scale-growth-interval", type=int, default=2000,
+                   help="--loss-scale dynamic: consecutive applied steps before the scale doubles")
     p.add_argument("--no-overlap-optimizer", action="store_true",
                    help="run AdamW after backward instead of per gradient bucket during backward")
     p.add_argument("--resubmit", choices=["none", "requeue", "chain"], default="none",
@@ -143,6 +151,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gemm-tuning", choices=["auto", "off", "tune"], default="auto")
     p.add_argument("--peak-tflops", type=float, default=2500.0, help="MFU denominator (MI355X dense bf16)")
     return p
+
+
+def _loss_scale(v: str):
+    """--loss-scale: 'off', 'dynamic', or a positive finite float (a fixed scale)."""
+    if v in ("off", "dynamic"):
+        return v
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if not (0.0 < f < float("inf")):
+        raise argparse.ArgumentTypeError(f"{v!r}: expected off, dynamic or a positive number")
+    return f
 
 
 def get_args(argv=None):

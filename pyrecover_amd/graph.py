@@ -12,6 +12,9 @@ What changes per step without re-capture:
   tensors;
 * learning rate and Adam bias corrections are uploaded to device memory
   (:meth:`FlatAdamW.begin_graph_step`) and read by the optimizer kernel;
+* with ``--loss-scale`` the loss scale, the decision to skip a non-finite step and the bias
+  corrections live in device memory (optim.adamw.LossScaleGuard, run in ``pre_step``): the captured
+  kernels read them, so a replay skips, halves or doubles without the host knowing;
 * checkpoint snapshot fences are applied to the stream *before* the replay (a captured graph
   cannot wait on an event recorded outside it), so a step never overtakes an in-flight
   checkpoint copy.
@@ -46,12 +49,14 @@ def capture_allowed(world_size: int) -> tuple:
 
 
 class StepGraph:
-    def __init__(self, model, optimizer, reducer=None, fences=None, pre_step=None):
+    def __init__(self, model, optimizer, reducer=None, fences=None, pre_step=None, loss_scale=None):
         self.model = model
         self.opt = optimizer
         self.reducer = reducer
         self.fences = list(fences or [])
-        self.pre_step = pre_step  # device-side work between backward and the update (grad clipping)
+        self.pre_step = pre_step  # device-side work between backward and the update (grad clipping, guard)
+        # the backward's seed (--loss-scale): a device scalar, or a callable returning one (or None)
+        self.loss_scale = loss_scale
         self.graph = None
         self.static_x = None
         self.static_y = None
@@ -68,7 +73,8 @@ class StepGraph:
             loss = self.model(self.static_x, labels=self.static_y, doc_start=self.static_ds)
         else:
             loss = self.model(self.static_x, labels=self.static_y)
-        loss.backward()
+        seed = self.loss_scale() if callable(self.loss_scale) else self.loss_scale
+        (loss if seed is None else loss * seed).backward()
         if self.reducer is not None:
             self.reducer.finish()
         if self.pre_step is not None:

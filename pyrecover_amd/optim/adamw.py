@@ -13,6 +13,10 @@ moments (``pra_adamw_master``), and the 16-bit parameters the model computes wit
 rounded once after every update. The master is saved as a third per-parameter state tensor
 (``state[i]["master_param"]``) next to the fp32 moments; a checkpoint without it (pure-bf16 runs,
 the reference's) resumes with the master taken from the loaded parameters.
+
+:class:`LossScaleGuard` (``--loss-scale``) keeps a loss scale and a per-step "gradient not finite"
+flag in device memory; with :meth:`FlatAdamW.enable_guard` every update kernel skips on that flag
+and the step count is the number of applied updates.
 """
 from __future__ import annotations
 
@@ -50,6 +54,108 @@ OPT_SCHED = os.environ.get("PYRECOVER_OPT_SCHED", "attn")
 # instead of ~60 VALU per element beside the attention backward; 7B B1 98.5 -> 97.2 ms, B16 within
 # noise, profiles/r3/step_ab_fast_*.log), whose p differs from torch's by a few fp32 ulps.
 FAST_MATH = os.environ.get("PYRECOVER_ADAMW_FAST", "0") == "1"
+
+
+class LossScaleGuard:
+    """Loss scale and non-finite step guard (``train.py --loss-scale``), state in device memory.
+
+    ``state`` is int32[8] on the parameters' device (layout: csrc/kernels/optim.hip
+    guard_finish_kernel): [0] scale (fp32 bits), [1] growth tracker, [2] found, [3] applied steps,
+    [4] skipped steps, [5] consecutive skips. :meth:`run` looks at the reduced gradient once per step,
+    between the backward and the update, and writes ``out`` = {unscaled norm, gradient multiplier}:
+
+    * sum of squares not finite: the step is skipped (``skip_dev`` = 1 makes every AdamW launch a
+      no-op, the multiplier is 0, the applied count stays); ``dynamic``: the scale halves;
+    * else the multiplier is ``clip / scale``, ``applied`` advances (AdamW's bias corrections follow
+      it, as torch's fused AdamW does with ``found_inf``); ``dynamic``: the scale doubles after
+      ``interval`` consecutive applied steps. No floor and no cap, as ``torch.amp.GradScaler``.
+
+    On the GPU this is one kernel behind the norm reduction and the host never reads the state
+    except in :meth:`read` (log steps, checkpoints), so a captured step replays with it. Without a
+    GPU the same rule runs in Python on the CPU tensors."""
+
+    SCALE, TRACKER, FOUND, APPLIED, SKIPPED, CONSECUTIVE = range(6)
+
+    def __init__(self, device, dynamic: bool = True, init_scale: float = 65536.0, growth_interval: int = 2000,
+                 max_norm: float = 0.0):
+        if not (init_scale > 0 and math.isfinite(init_scale)):
+            raise ValueError(f"loss scale must be positive and finite, got {init_scale}")
+        if int(growth_interval) < 1:
+            raise ValueError("loss-scale growth interval must be at least 1")
+        self.dynamic = bool(dynamic)
+        self.interval = int(growth_interval)
+        self.max_norm = float(max_norm)  # > 0: clip the unscaled norm to it (--clip-grad)
+        self.state = torch.zeros(8, dtype=torch.int32, device=device)
+        self.out = torch.zeros(2, dtype=torch.float32, device=device)
+        self.scale_dev = self.state[0:1].view(torch.float32)  # fp32[1]: the backward's seed
+        self.skip_dev = self.state[2:3]
+        self.scale_dev.fill_(float(init_scale))
+        self.hyper: Optional[torch.Tensor] = None  # the optimizer's hyper_dev (FlatAdamW.enable_guard)
+        self.betas = (0.9, 0.999)
+        # the HIP kernel decides; False: the same rule in Python (CPU runs, fp64 models on the GPU)
+        self.native = self.state.is_cuda
+
+    @property
+    def multiplier(self) -> torch.Tensor:
+        """fp32[1]: the AdamW kernels' ``gscale_dev`` (0 on a skipped step, else clip / scale)."""
+        return self.out[1:2]
+
+    def run(self, grad: Optional[torch.Tensor] = None, pre_scale: float = 1.0, sq: Optional[torch.Tensor] = None):
+        """One guard step over the reduced gradient ``grad``, or over its squared norm ``sq`` (fp64[1],
+        already summed over the ranks: sharded optimizer). ``pre_scale``: the gradient's static factor
+        (1 / (world size x accumulation steps)), so the norm is that of the mean gradient."""
+        if (grad is None) == (sq is None):
+            raise ValueError("exactly one of grad and sq")
+        if self.native:
+            _ext.require_for(self.state).guard_step_(grad, sq, self.state, self.out, self.hyper, self.max_norm,
+                                                     pre_scale, self.dynamic, self.interval, *self.betas)
+            return
+        if sq is None:
+            sq = grad.to(torch.promote_types(grad.dtype, torch.float32)).pow(2).sum()
+        sq = float(sq)
+        st = self.state
+        scale = float(self.scale_dev[0])
+        self.out[0] = (math.sqrt(sq) if math.isfinite(sq) else sq) * pre_scale / scale
+        if not math.isfinite(sq):
+            self.out[1] = 0.0
+            st[self.FOUND] = 1
+            st[self.SKIPPED] += 1
+            st[self.CONSECUTIVE] += 1
+            if self.dynamic:
+                self.scale_dev[0] = scale * 0.5
+                st[self.TRACKER] = 0
+            return
+        clip = min(1.0, self.max_norm / (float(self.out[0]) + 1e-6)) if self.max_norm > 0 else 1.0
+        self.out[1] = clip / scale
+        st[self.FOUND] = 0
+        st[self.APPLIED] += 1
+        st[self.CONSECUTIVE] = 0
+        if self.dynamic:
+            st[self.TRACKER] += 1
+            if int(st[self.TRACKER]) == self.interval:
+                self.scale_dev[0] = scale * 2.0
+                st[self.TRACKER] = 0
+
+    def read(self) -> dict:
+        """Host copy of the state (synchronizes with the device: log steps and checkpoints only)."""
+        st = self.state.cpu()
+        return {"scale": float(st[0:1].view(torch.float32)[0]), "tracker": int(st[1]), "found": int(st[2]),
+                "applied": int(st[3]), "skipped_total": int(st[4]), "consecutive_skips": int(st[5]),
+                "grad_norm": float(self.out[0])}
+
+    def state_dict(self) -> dict:
+        r = self.read()
+        return {k: r[k] for k in ("scale", "tracker", "applied", "skipped_total")}
+
+    def load_state_dict(self, sd: dict):
+        st = torch.zeros(8, dtype=torch.int32)
+        st[0:1].view(torch.float32)[0] = float(sd["scale"])
+        st[self.TRACKER], st[self.APPLIED] = int(sd["tracker"]), int(sd["applied"])
+        st[self.SKIPPED] = int(sd["skipped_total"])
+        self.state.copy_(st)
+
+    def set_applied(self, n: int):
+        self.state[self.APPLIED:self.APPLIED + 1].fill_(int(n))
 
 
 class FlatAdamW(torch.optim.AdamW):
@@ -94,6 +200,47 @@ class FlatAdamW(torch.optim.AdamW):
         self.hyper: Optional[torch.Tensor] = None
         self._hyper_ring = []
         self._hyper_slot = 0
+        self.guard: Optional[LossScaleGuard] = None  # --loss-scale: device-side skip / scale decisions
+
+    # --- loss scale / non-finite step guard ---------------------------------------------------
+    def enable_guard(self, guard: LossScaleGuard):
+        """Every update takes its gradient multiplier, its skip flag and (GPU) its bias corrections from
+        ``guard``, which the caller runs once per step between the backward and :meth:`step`
+        (:meth:`LossScaleGuard.run`). The step count becomes the guard's applied count: it does not
+        advance on a skipped step, and the host reads it only in :meth:`state_dict` / :meth:`applied_steps`.
+        On the GPU the kernels always read ``hyper``; the host uploads only the learning rate."""
+        self.guard = guard
+        guard.betas = tuple(float(b) for b in self.param_groups[0]["betas"])
+        guard.set_applied(self._step)
+        self.grad_scale_dev = guard.multiplier
+        guard.native = _ext.hip(self.flat.data)
+        if guard.native:
+            self._alloc_hyper()
+            guard.hyper = self.hyper
+
+    def applied_steps(self) -> int:
+        """Updates applied so far (guard mode: read from the device, which synchronizes)."""
+        if self.guard is not None:
+            self._step = self.guard.read()["applied"]
+        return self._step
+
+    def _alloc_hyper(self):
+        if self.hyper is None:
+            self.hyper = torch.zeros(3, dtype=torch.float64, device=self.flat.data.device)
+            # pinned staging ring: a slot is rewritten only after its previous H2D copy completed
+            self._hyper_ring = [(torch.zeros(3, dtype=torch.float64).pin_memory(), torch.cuda.Event())
+                                for _ in range(4)]
+
+    def _upload_hyper(self):
+        """{lr, bc1, bc2_sqrt} -> ``hyper``; guard mode: lr only (the guard kernel writes the rest)."""
+        lr, _, _, _, _, bc1, bc2_sqrt = self._coeffs()
+        host, ev = self._hyper_ring[self._hyper_slot]
+        self._hyper_slot = (self._hyper_slot + 1) % len(self._hyper_ring)
+        ev.synchronize()
+        host[0], host[1], host[2] = lr, bc1, bc2_sqrt
+        n = 1 if self.guard is not None else 3
+        self.hyper[:n].copy_(host[:n], non_blocking=True)
+        ev.record()
 
     # --- captured-step (HIP graph) support ---------------------------------------------------
     def enable_graph_mode(self):
@@ -103,21 +250,13 @@ class FlatAdamW(torch.optim.AdamW):
         if not self.flat.data.is_cuda:
             raise RuntimeError("graph mode needs the parameters on a GPU")
         self.graph_mode = True
-        dev = self.flat.data.device
-        self.hyper = torch.zeros(3, dtype=torch.float64, device=dev)
-        # pinned staging ring: a slot is rewritten only after its previous H2D copy completed
-        self._hyper_ring = [(torch.zeros(3, dtype=torch.float64).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        self._alloc_hyper()
 
     def begin_graph_step(self):
         """Host side of one replayed step: advance the step count and upload the scalars."""
-        self._step += 1
-        lr, _, _, _, _, bc1, bc2_sqrt = self._coeffs()
-        host, ev = self._hyper_ring[self._hyper_slot]
-        self._hyper_slot = (self._hyper_slot + 1) % len(self._hyper_ring)
-        ev.synchronize()
-        host[0], host[1], host[2] = lr, bc1, bc2_sqrt
-        self.hyper.copy_(host, non_blocking=True)
-        ev.record()
+        if self.guard is None:  # guard mode: the applied count lives on the device
+            self._step += 1
+        self._upload_hyper()
 
     # --- overlapped update (optimizer-in-backward) ----------------------------------------
     def enable_overlap(self, reducer):
@@ -146,24 +285,25 @@ class FlatAdamW(torch.optim.AdamW):
         args = (lr, b1, b2, eps, wd, bc1, bc2_sqrt, self.grad_scale, self.grad_scale_dev, self.hyper)
         m, v = self.exp_avg, self.exp_avg_sq
 
-        fast = FAST_MATH
+        # (fast, skip_dev): a null skip_dev is the kernels' unguarded path
+        tail = (FAST_MATH, self.guard.skip_dev) if self.guard is not None else (FAST_MATH,)
         sharded = self._sharded()
         if self.master is not None:
             # fp32 master update, then the transposed shadows of the matrices in range from the
             # rounded parameters (same stream: the next backward sees them; sharded: after the gather)
-            C.adamw_master_(f.data[lo:hi], self.master[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, fast)
+            C.adamw_master_(f.data[lo:hi], self.master[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, *tail)
             if not sharded:
                 f.refresh_transposed(lo, hi)
             return
         if sharded:
             # an owned chunk cuts matrices: plain update; the shadows are re-derived from the gathered
             # parameters (step)
-            C.adamw_flat_(f.data[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, fast)
+            C.adamw_flat_(f.data[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, *tail)
             return
 
         def flat_update(a, b):
             if a < b:
-                C.adamw_flat_(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, fast)
+                C.adamw_flat_(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, *tail)
 
         mats = f.transposed_in(lo, hi) if FUSED_T else []
         cur = lo
@@ -176,7 +316,7 @@ class FlatAdamW(torch.optim.AdamW):
             flat_update(cur, o)
             sl = slice(o, o + n)
             C.adamw_t_(f.data[sl].view(rows, cols), f.grad[sl].view(rows, cols), m[sl].view(rows, cols),
-                       v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, fast)
+                       v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, *tail)
             cur = o + n
         flat_update(cur, hi)
         if not FUSED_T:
@@ -307,7 +447,15 @@ class FlatAdamW(torch.optim.AdamW):
             self._done_ranges = []
             return loss
         g = self.param_groups[0]
-        if not self.graph_mode:
+        if self.guard is not None:
+            # the guard ran on this step's gradient (LossScaleGuard.run). GPU: skip flag, multiplier and
+            # bias corrections are in device memory; CPU: the applied count is read here
+            if self.guard.native:
+                if not self.graph_mode:
+                    self._upload_hyper()
+            else:
+                self._step = int(self.guard.state[LossScaleGuard.APPLIED])
+        elif not self.graph_mode:
             self._step += 1
         b1, b2 = g["betas"]
         lr, eps, wd = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
@@ -327,6 +475,8 @@ class FlatAdamW(torch.optim.AdamW):
     def _step_reference(self, lr, b1, b2, eps, wd, bc1, bc2_sqrt, lo=0, hi=None):
         f = self.flat
         hi = f.numel if hi is None else hi
+        if self.guard is not None and int(self.guard.state[LossScaleGuard.FOUND]):
+            return  # skipped step: parameters, moments and the master stay as they are
         gs = self.grad_scale * (float(self.grad_scale_dev[0]) if self.grad_scale_dev is not None else 1.0)
         # `.data`: the update must not bump the flat buffer's autograd version counter (shared by
         # every parameter view), or an overlapped bucket update during backward would invalidate
@@ -357,6 +507,7 @@ class FlatAdamW(torch.optim.AdamW):
         return n + (self.master.nbytes if self.master is not None else 0)
 
     def state_dict(self):
+        self.applied_steps()  # guard mode: the applied count, from the device
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._step), dtype=torch.float32)
         return super().state_dict()
@@ -397,5 +548,7 @@ class FlatAdamW(torch.optim.AdamW):
         if len(steps) > 1:
             raise ValueError(f"inconsistent per-parameter step counts {sorted(steps)}")
         self._step = int(steps.pop()) if steps else 0
+        if self.guard is not None:
+            self.guard.set_applied(self._step)
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._step), dtype=torch.float32)

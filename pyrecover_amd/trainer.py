@@ -38,7 +38,7 @@ from .data.dataset import (CollatorForCLM, CollatorForPackedCLM, PackedParquetDa
 from .data.sampler import ResumableDistributedSampler
 from .data.tokenizer import load_tokenizer
 from .models.llama import Transformer
-from .optim.adamw import FlatAdamW
+from .optim.adamw import FlatAdamW, LossScaleGuard
 from .optim.lr import build_lr_scheduler
 from .parallel import dist as D
 from .parallel.ddp import GradReducer, broadcast_flat
@@ -232,7 +232,11 @@ def train(args):
     # the sharded optimizer's owned chunks cut matrices: no transposed weight shadows (each would be
     # re-derived from the gathered parameters every step)
     flat = model.flatten_(tokens_per_step=local_batch_size * seq_len, shadows=False if shard else None)
-    overlap = not (args.clip_grad or args.no_overlap_optimizer)
+    loss_scale = getattr(args, "loss_scale", "off")
+    nan_step, nan_rank = _nan_grad_fault()
+    # a global decision (clip coefficient, non-finite guard, injected value) needs the whole reduced
+    # gradient before any update: the update then runs after the backward
+    overlap = not (args.clip_grad or args.no_overlap_optimizer or loss_scale != "off" or nan_step is not None)
     reducer = None
     if is_dist:
         broadcast_flat(flat)
@@ -273,6 +277,41 @@ def train(args):
     if optimizer.master is not None:
         log_rank0(f"fp32 master weights: {optimizer.master.numel() * 4 / 2**30:.2f} GiB "
                   f"(+ fp32 moments {2 * optimizer.exp_avg.numel() * 4 / 2**30:.2f} GiB)")
+    guard = None
+    if loss_scale != "off":
+        dynamic = loss_scale == "dynamic"
+        guard = LossScaleGuard(device, dynamic=dynamic,
+                               init_scale=float(getattr(args, "loss_scale_init", 65536.0)) if dynamic else float(loss_scale),
+                               growth_interval=int(getattr(args, "loss_scale_growth_interval", 2000)),
+                               max_norm=float(args.grad_max_norm) if args.clip_grad else 0.0)
+        optimizer.enable_guard(guard)
+        log_rank0(f"Loss scale: {'dynamic from' if dynamic else 'fixed'} {float(guard.scale_dev[0]):g}"
+                  + (f", x2 after {guard.interval} applied steps, x0.5 on a skipped step" if dynamic else "")
+                  + "; a step whose reduced gradient is not finite is skipped on the device")
+    poison = None
+    if nan_step is not None:
+        # PYRECOVER_FAULT=nan_grad:<step>[:<rank>]: a device scalar (NaN at that step, else 0) added to one
+        # gradient element before the update; with a rank, to that rank's backward seed instead, so the
+        # value reaches the other ranks through the gradient reduction
+        poison = torch.zeros((), dtype=torch.float32, device=device)
+
+    def pre_update():
+        """Device-side work between the reduced backward and the update (also a captured step's)."""
+        if poison is not None and nan_rank is None:
+            flat.grad[0:1].add_(poison.to(flat.grad.dtype))
+        if guard is not None or args.clip_grad:
+            coef = _clip_coef(flat, args.grad_max_norm, grad_scale, reducer, guard)
+            if guard is None:
+                optimizer.grad_scale_dev = coef
+
+    def backward_seed():
+        """What the backward is seeded with: the loss scale, a device scalar (it changes without a host
+        sync), or None for a plain backward."""
+        scale = guard.scale_dev.reshape(()) if guard is not None else None
+        if poison is not None and nan_rank is not None:
+            return poison + (scale if scale is not None else 1.0)
+        return scale
+
     if overlap:
         optimizer.enable_overlap(reducer)
         optimizer.pre_update_fences.append(ckcore.fence_all)
@@ -291,9 +330,9 @@ def train(args):
         elif use_cuda:
             from .graph import StepGraph
 
-            pre = (lambda: setattr(optimizer, "grad_scale_dev",
-                                   _clip_coef(flat, args.grad_max_norm, grad_scale, reducer))) if args.clip_grad else None
-            step_graph = StepGraph(model, optimizer, reducer, fences=[ckcore.fence_all], pre_step=pre)
+            pre = pre_update if (args.clip_grad or guard is not None or poison is not None) else None
+            step_graph = StepGraph(model, optimizer, reducer, fences=[ckcore.fence_all], pre_step=pre,
+                                   loss_scale=backward_seed if (guard is not None or poison is not None) else None)
             log_rank0(f"--compile: the training step is captured into a HIP graph after "
                       f"{args.compile_warmup_steps} eager steps and replayed (no Inductor/Triton)")
         else:
@@ -486,6 +525,9 @@ def train(args):
             micro.append((input_ids.to(device, non_blocking=True), labels.to(device, non_blocking=True),
                           doc_start.to(device, non_blocking=True) if doc_start is not None else None))
 
+        if poison is not None:
+            on = train_step == nan_step and (nan_rank is None or nan_rank == rank)
+            poison.fill_(float("nan") if on else 0.0)
         if step_graph is not None and eager_steps_this_run >= args.compile_warmup_steps:
             loss = step_graph.step(*micro[0])  # fences the snapshot before the replay
         else:
@@ -501,14 +543,14 @@ def train(args):
                     reducer.enabled = m == accum - 1
                 lm = (model(input_ids, labels=labels) if doc_start is None
                       else model(input_ids, labels=labels, doc_start=doc_start))
-                lm.backward()
+                sd = backward_seed()
+                (lm if sd is None else lm * sd).backward()  # the logged loss stays unscaled
                 loss = lm.detach() if loss is None else loss + lm.detach()
             if accum > 1:
                 loss = loss / accum
             if reducer is not None:
                 reducer.finish()
-            if args.clip_grad:
-                optimizer.grad_scale_dev = _clip_coef(flat, args.grad_max_norm, grad_scale, reducer)
+            pre_update()
             ckcore.fence_all()  # an async snapshot must land before parameters change
             optimizer.step()
             eager_steps_this_run += 1
@@ -522,6 +564,7 @@ def train(args):
             # sync first: the host runs ahead of the GPU, so an unsynchronized clock would count
             # queued-but-unexecuted steps (the reference reads the clock before its .item())
             lval = loss.item()
+            gstate = guard.read() if guard is not None else None  # the host has just synchronized
             time_delta = time.perf_counter() - time_last_log
             tps = ntokens_since_last_log / time_delta
             per_gpu = tps / world_size
@@ -538,10 +581,22 @@ def train(args):
                        "nonpad_fraction": nonpad_since_last_log / max(rows_since_last_log * seq_len, 1),
                        "time": time.time()}
                 rec.update(_diagnostics(step_timer, device, comm_timer, world_size, ckpt_window, stopper))
+                if gstate is not None:
+                    gn = gstate["grad_norm"]  # of the last step; not finite (null) when it was skipped
+                    rec.update(loss_scale=gstate["scale"], skipped_steps=gstate["skipped_total"],
+                               grad_norm=gn if gn == gn and abs(gn) != float("inf") else None)
                 metrics_f.write(json.dumps(rec) + "\n")
                 metrics_f.flush()
             elif comm_timer is not None:
                 comm_timer.steps.clear()
+            if gstate is not None:
+                log_rank0(f"Loss scale: {gstate['scale']:g} | Skipped steps: {gstate['skipped_total']} | "
+                          f"Grad norm: {gstate['grad_norm']:.4g}")
+                if gstate["consecutive_skips"] >= MAX_CONSECUTIVE_SKIPS:
+                    raise RuntimeError(f"--loss-scale: the last {gstate['consecutive_skips']} steps were all skipped "
+                                       f"(non-finite gradients; loss scale now {gstate['scale']:g}, step {train_step}): "
+                                       f"the run is not training. Parameters and optimizer state are unchanged since "
+                                       f"the last applied step ({gstate['applied']} applied)")
             ckpt_window.clear()
             ntokens_since_last_log = 0
             ntraining_tokens_since_last_log = 0
@@ -678,10 +733,15 @@ def _diagnostics(step_timer, device, comm_timer, world_size, ckpt_window, stoppe
     return out
 
 
-def _clip_coef(flat, max_norm: float, pre_scale: float, reducer=None):
+def _clip_coef(flat, max_norm: float, pre_scale: float, reducer=None, guard=None):
     """Device-side clip coefficient min(1, max_norm / ||g||) over the flat (reduced) gradient. With
     the sharded optimizer each rank holds only its chunks reduced: the squared norms of those (the
-    shared tails counted on rank 0 only) are summed over the ranks."""
+    shared tails counted on rank 0 only) are summed over the ranks.
+
+    With ``guard`` (--loss-scale) the same reduction feeds the guard step instead: it decides from
+    the sum of squares (inf and NaN survive the sums, and the all-reduce: every rank decides alike)
+    whether the update runs, keeps the scale state, and its multiplier -- clip / scale, the clip taken
+    on the unscaled norm, 0 on a skipped step -- is returned."""
     from . import _ext
 
     if reducer is not None and reducer.shard:
@@ -697,12 +757,34 @@ def _clip_coef(flat, max_norm: float, pre_scale: float, reducer=None):
         sq = torch.stack(parts).sum().reshape(1) if parts else torch.zeros(1, dtype=torch.float64,
                                                                            device=flat.grad.device)
         torch.distributed.all_reduce(sq, group=reducer.group)
+        if guard is not None:
+            guard.run(sq=sq, pre_scale=pre_scale)
+            return guard.multiplier
         norm = sq.sqrt() * pre_scale
         return torch.clamp(max_norm / (norm + 1e-6), max=1.0).reshape(1).float()
+    if guard is not None:
+        guard.run(flat.grad, pre_scale=pre_scale)
+        return guard.multiplier
     if _ext.hip(flat.grad):
         return _ext.native().grad_norm(flat.grad, max_norm, pre_scale)[1:2]
     norm = flat.grad.to(torch.promote_types(flat.grad.dtype, torch.float32)).norm() * pre_scale
     return torch.clamp(max_norm / (norm + 1e-6), max=1.0).reshape(1).float()
+
+
+MAX_CONSECUTIVE_SKIPS = 25  # --loss-scale: this many skipped steps in a row end the run at a log step
+
+
+def _nan_grad_fault():
+    """``PYRECOVER_FAULT=nan_grad:<step>[:<rank>]`` -> (step, rank or None), else (None, None): at that
+    training step a NaN is added to one element of the reduced gradient before the update (with a
+    rank: to that rank's backward seed, so only that rank's local gradient is poisoned). The value
+    sits in a device scalar the host sets each step, so a replayed captured step injects it too. It
+    injects a value, not a device fault."""
+    spec = os.environ.get("PYRECOVER_FAULT", "")
+    if not spec.startswith("nan_grad:"):
+        return None, None
+    parts = spec.split(":")
+    return int(parts[1]), (int(parts[2]) if len(parts) > 2 else None)
 
 
 def _replica_check(flat, optimizer, step: int):

@@ -29,7 +29,10 @@ def parse_arm(spec):
     attention kernel option (_ext.set_attn_options); `native.SETTER=value` calls that setter of the
     extension before the arm's steps and with 0 after them; the item `noupdate` skips the AdamW update
     kernels (a diagnostic arm: what the optimizer costs the step); the item `docs=N` runs the arm's
-    steps on packed batches of N equal documents per row (doc_start: document-masked attention)."""
+    steps on packed batches of N equal documents per row (doc_start: document-masked attention); the
+    item `clip=MAX_NORM` runs them as --clip-grad does (gradient norm, then the update after the
+    backward), `guard=SCALE` as --loss-scale SCALE does (scaled backward, guard kernel, guarded update
+    after the backward)."""
     name, _, body = spec.partition(":")
     sets = []
     for item in filter(None, body.split(";")):
@@ -39,6 +42,9 @@ def parse_arm(spec):
         lhs, _, rhs = item.partition("=")
         if lhs.strip() == "docs":
             sets.append(("docs", "docs", int(rhs)))
+            continue
+        if lhs.strip() in ("clip", "guard"):
+            sets.append(("mode", lhs.strip(), float(rhs)))
             continue
         mod, _, attr = lhs.strip().rpartition(".")
         if mod in ("attn", "native"):  # attention option / native setter C.<attr>(value), reset to 0 after
@@ -64,7 +70,7 @@ def main():
     configure_gemm_tuning("auto")
     from pyrecover_amd.config import get_preset
     from pyrecover_amd.models.llama import Transformer
-    from pyrecover_amd.optim.adamw import FlatAdamW
+    from pyrecover_amd.optim.adamw import FlatAdamW, LossScaleGuard
     from pyrecover_amd.parallel.ddp import GradReducer
 
     arms = [parse_arm(s) for s in a.arm]
@@ -85,7 +91,7 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
 
-    def step(docs=0):
+    def step(docs=0, clip=0.0, guard=None):
         t = torch.randint(0, cfg.vocab_size, (B, S + 1), device=dev, generator=gen)
         opt.zero_grad()
         if docs:
@@ -94,8 +100,12 @@ def main():
             loss = model(t[:, :-1], labels=t[:, 1:], doc_start=ds)
         else:
             loss = model(t[:, :-1], labels=t[:, 1:])
-        loss.backward()
+        (loss if guard is None else loss * guard.scale_dev.reshape(())).backward()
         reducer.finish()
+        if guard is not None:
+            guard.run(flat.grad, pre_scale=1.0)
+        elif clip:
+            opt.grad_scale_dev = _ext.native().grad_norm(flat.grad, clip, 1.0)[1:2]
         opt.step()
         return loss
 
@@ -104,7 +114,7 @@ def main():
     def resolve(sets):
         out = []
         for m, k, v in sets:
-            if m in ("attn", "native", "docs"):
+            if m in ("attn", "native", "docs", "mode"):
                 continue
             m = opt if m == "opt" else m
             if v == "noupdate":
@@ -117,6 +127,13 @@ def main():
         prev_attn = _ext.set_attn_options(**attn) if attn else None
         docs = max([v for m, _, v in arm[1] if m == "docs"] or [0])
         natives = [(k, v) for m, k, v in arm[1] if m == "native"]
+        mode = {k: v for m, k, v in arm[1] if m == "mode"}
+        guard = None
+        if "guard" in mode:  # the update leaves the backward: every launch guarded, scalars from device memory
+            guard = LossScaleGuard(dev, dynamic=False, init_scale=mode["guard"])
+            opt.enable_guard(guard)
+        elif "clip" in mode:
+            opt.grad_scale_dev = torch.ones(1, device=dev)  # set before the backward: no overlapped update
         for k, v in natives:
             getattr(_ext.native(), k)(v)
         sets = resolve(arm[1])
@@ -127,10 +144,12 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(n):
-                loss = step(docs)
+                loss = step(docs, mode.get("clip", 0.0), guard)
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1000 / n, float(loss.item())
         finally:
+            if mode:  # back to the overlapped, unguarded update with host scalars
+                opt.guard, opt.grad_scale_dev, opt.hyper = None, None, None
             for k, _ in natives:
                 getattr(_ext.native(), k)(0)
             if prev_attn is not None:
