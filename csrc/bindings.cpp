@@ -510,6 +510,101 @@ void adamw_t_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at:
         "adamw_t");
 }
 
+// Arguments the stochastic-rounding AdamW launches add (csrc/kernels/philox_sr.h).
+static const int* sr_args(const char* what, const at::Tensor& p, int64_t base, int64_t step, int64_t mask,
+                          const c10::optional<at::Tensor>& step_dev) {
+  TORCH_CHECK(p.scalar_type() == at::kBFloat16 || p.scalar_type() == at::kHalf, what,
+              ": stochastic rounding needs bf16 or fp16 parameters and moments");
+  TORCH_CHECK(base >= 0 && base % 8 == 0, what, ": base must be >= 0 and a multiple of 8, got ", base);
+  TORCH_CHECK(mask >= 1 && mask <= 7, what, ": mask must be in 1..7, got ", mask);
+  TORCH_CHECK(step >= 0 && step <= INT32_MAX, what, ": step");
+  if (!step_dev.has_value()) return nullptr;
+  TORCH_CHECK(step_dev->scalar_type() == at::kInt && step_dev->numel() >= 1, what, ": step_dev int32");
+  same_dev(p, *step_dev, "step_dev");
+  return step_dev->data_ptr<int>();
+}
+
+// adamw_flat_ for 16-bit state with the tensors in `mask` (bit 0 p, 1 exp_avg, 2 exp_avg_sq) rounded
+// stochastically; p[0] is flat position `base`, the step number is `step` or (when given) step_dev[0].
+void adamw_flat_sr_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, double lr, double b1, double b2,
+                    double eps, double wd, double bc1, double bc2_sqrt, double gscale,
+                    const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
+                    const c10::optional<at::Tensor>& skip_dev, uint64_t seed, int64_t base, int64_t step,
+                    const c10::optional<at::Tensor>& step_dev, int64_t mask) {
+  const Range range_("pyrecover::adamw_flat_sr");
+  check_dev(p, "p");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), "adamw_sr: contiguous");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adamw_sr: sizes");
+  TORCH_CHECK(g.scalar_type() == p.scalar_type() && m.scalar_type() == p.scalar_type() &&
+                  v.scalar_type() == p.scalar_type(), "adamw_sr: dtypes must match");
+  same_dev(p, g, "grad");
+  same_dev(p, m, "exp_avg");
+  same_dev(p, v, "exp_avg_sq");
+  const int* std_ = sr_args("adamw_flat_sr", p, base, step, mask, step_dev);
+  for (const at::Tensor& t : {p, g, m, v})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw_flat_sr: operands must be 16-B aligned");
+  const c10::DeviceGuard guard(p.device());
+  const float* gsd = nullptr;
+  if (gscale_dev.has_value()) {
+    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_sr: gscale_dev fp32");
+    same_dev(p, *gscale_dev, "gscale_dev");
+    gsd = gscale_dev->data_ptr<float>();
+  }
+  const double* hyd = nullptr;
+  if (hyper_dev.has_value()) {
+    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_sr: hyper_dev fp64[3]");
+    same_dev(p, *hyper_dev, "hyper_dev");
+    hyd = hyper_dev->data_ptr<double>();
+  }
+  const int* skd = skip_flag(p, skip_dev);
+  check(pra_adamw_flat_sr(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1, b2, eps,
+                          wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd, seed, base, (int)step, std_,
+                          (int)mask, stream_of(p)),
+        "adamw_flat_sr");
+}
+
+// adamw_t_ with stochastic rounding; p[0][0] is flat position `base`, pt takes the rounded p.
+void adamw_t_sr_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor pt, double lr, double b1,
+                 double b2, double eps, double wd, double bc1, double bc2_sqrt, double gscale,
+                 const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
+                 const c10::optional<at::Tensor>& skip_dev, uint64_t seed, int64_t base, int64_t step,
+                 const c10::optional<at::Tensor>& step_dev, int64_t mask) {
+  const Range range_("pyrecover::adamw_t_sr");
+  check_dev(p, "p");
+  TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && g.sizes() == p.sizes() && m.sizes() == p.sizes() &&
+                  v.sizes() == p.sizes() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
+              "adamw_t_sr: p/g/m/v must be contiguous [rows, cols]");
+  const int64_t rows = p.size(0), cols = p.size(1);
+  TORCH_CHECK(pt.dim() == 2 && pt.size(0) == cols && pt.size(1) == rows && pt.is_contiguous(),
+              "adamw_t_sr: pt [cols, rows]");
+  TORCH_CHECK(rows % 64 == 0 && cols % 64 == 0, "adamw_t_sr: rows and cols must be multiples of 64");
+  for (const at::Tensor& t : {g, m, v, pt}) {
+    same_dev(p, t, "adamw_t_sr operand");
+    TORCH_CHECK(t.scalar_type() == p.scalar_type(), "adamw_t_sr: dtypes must match");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw_t_sr: operands must be 16-B aligned");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0, "adamw_t_sr: p must be 16-B aligned");
+  const int* std_ = sr_args("adamw_t_sr", p, base, step, mask, step_dev);
+  const c10::DeviceGuard guard(p.device());
+  const float* gsd = nullptr;
+  if (gscale_dev.has_value()) {
+    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_t_sr: gscale_dev fp32");
+    same_dev(p, *gscale_dev, "gscale_dev");
+    gsd = gscale_dev->data_ptr<float>();
+  }
+  const double* hyd = nullptr;
+  if (hyper_dev.has_value()) {
+    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_t_sr: hyper_dev fp64[3]");
+    same_dev(p, *hyper_dev, "hyper_dev");
+    hyd = hyper_dev->data_ptr<double>();
+  }
+  const int* skd = skip_flag(p, skip_dev);
+  check(pra_adamw_t_sr(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)rows,
+                       (int)cols, lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd, seed,
+                       base, (int)step, std_, (int)mask, stream_of(p)),
+        "adamw_t_sr");
+}
+
 // dst = src^T for a 2-D 16-bit tensor (bf16/fp16) with R, C multiples of 64 (dst: optional
 // preallocated [C, R] row-major output).
 at::Tensor transpose2d(const at::Tensor& src, c10::optional<at::Tensor> out) {
@@ -964,7 +1059,17 @@ PYBIND11_MODULE(_C, m) {
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
         py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
         py::arg("fast") = false, py::arg("skip_dev") = py::none());
-  m.def("adamw_master_", &adamw_master_, py::arg("p"), py::arg("pm"), py::arg("g"), py::arg("m"), py::arg("v"),
+  m.def("adamw_flat_sr_", &adamw_flat_sr_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
+        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
+        py::arg("fast") = false, py::arg("skip_dev") = py::none(), py::kw_only(), py::arg("seed"), py::arg("base"),
+        py::arg("step"), py::arg("step_dev") = py::none(), py::arg("mask"));
+  m.def("adamw_t_sr_", &adamw_t_sr_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("pt"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
+        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
+        py::arg("fast") = false, py::arg("skip_dev") = py::none(), py::kw_only(), py::arg("seed"), py::arg("base"),
+        py::arg("step"), py::arg("step_dev") = py::none(), py::arg("mask"));
+  m.def("adamw_master_", &adamw_master_,py::arg("p"), py::arg("pm"), py::arg("g"), py::arg("m"), py::arg("v"),
         py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
         py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
         py::arg("fast") = false, py::arg("skip_dev") = py::none());

@@ -95,6 +95,18 @@ hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void
                        double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
                        const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
     hipStream_t s);
+// Stochastic rounding of 16-bit p / exp_avg / exp_avg_sq (philox_sr.h): mask bit 0 / 1 / 2; base: flat
+// position of the first element (>= 0, % 8 == 0); step_dev (device int32), when non-null, replaces step
+hipError_t pra_adamw_flat_sr(int dtype, void* p, const void* g, void* m, void* v, long n, double lr, double b1,
+                             double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
+                             const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+                             unsigned long long seed, long long base, int step, const int* step_dev, int mask,
+                             hipStream_t s);
+hipError_t pra_adamw_t_sr(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
+                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
+                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+                          unsigned long long seed, long long base, int step, const int* step_dev, int mask,
+                          hipStream_t s);
 
 hipError_t pra_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
                         int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal,

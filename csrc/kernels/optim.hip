@@ -22,6 +22,7 @@
 // gradient is not finite, guard_finish_kernel below); a zero multiplier alone would still decay the
 // weights and the moments. A null `skip_dev` is the unguarded path.
 #include "common.h"
+#include "philox_sr.h"
 
 namespace pra {
 
@@ -179,18 +180,44 @@ __global__ __launch_bounds__(256) void adamw_kernel(P* __restrict__ p, const P* 
   }
 }
 
+// 16 B of T from 8 fp32 values of the chunk at flat position idx: stochastically rounded when the
+// tensor's bit of the (block-uniform) mask is set, else exactly as pack8 stores them.
+template <typename P>
+__device__ __forceinline__ pra_u32x4 pack8_sr(const float (&v)[8], bool sr_on, const SrArgs& sr, long long idx,
+                                              uint32_t step, uint32_t stream) {
+  if (!sr_on) return pack8<P>(v);
+  uint32_t rnd[4], w[4];
+  sr_chunk_bits(sr.seed, idx, step, stream, rnd);
+  sr_pack8<P>(v, rnd, w);
+  pra_u32x4 o;
+  o[0] = w[0];
+  o[1] = w[1];
+  o[2] = w[2];
+  o[3] = w[3];
+  return o;
+}
+template <typename P>
+__device__ __forceinline__ P from_f_sr(float x, bool sr_on, const SrArgs& sr, long long idx, uint32_t step,
+                                       uint32_t stream) {
+  if (!sr_on) return from_f<P>(x);
+  return __builtin_bit_cast(P, sr_round_at<P>(x, sr.seed, idx, step, stream));
+}
+
 // Flat 16-bit AdamW (p, g, m, v of one dtype): U chunks of 8 per thread, all their loads issued
 // before the math (more bytes in flight per wave), non-temporal. Same math as adamw_kernel.
-template <typename P, bool FAST, int U>
+// SR (pra_adamw_flat_sr): the tensors in sr.mask are rounded stochastically (philox_sr.h) from the
+// same fp32 adamw_elem results; element o of the launch is flat position sr.base + o.
+template <typename P, bool FAST, int U, bool SR = false>
 __global__ __launch_bounds__(256) void adamw16_kernel(P* __restrict__ p, const P* __restrict__ g, P* __restrict__ m,
                                                       P* __restrict__ v, long n, double lr, double b1, double b2,
                                                       double eps, double wd, double bc1, double bc2_sqrt, float gscale,
                                                       const float* __restrict__ gscale_dev,
                                                       const double* __restrict__ hyper_dev,
-                                                    const int* __restrict__ skip_dev) {
+                                                      const int* __restrict__ skip_dev, SrArgs sr) {
   if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
+  [[maybe_unused]] const uint32_t t = SR ? (uint32_t)(sr.step_dev ? *sr.step_dev : sr.step) : 0u;
   const long n8 = n / 8, stride = (long)gridDim.x * 256 * U;
   for (long i0 = (long)blockIdx.x * 256 * U + threadIdx.x; i0 < n8; i0 += stride) {
     float pv[U][8], gv[U][8], mv[U][8], vv[U][8];
@@ -210,18 +237,30 @@ __global__ __launch_bounds__(256) void adamw16_kernel(P* __restrict__ p, const P
       if (i0 + 256 * u < n8) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) adamw_elem<FAST>(pv[u][j], mv[u][j], vv[u][j], gv[u][j], gs, c);
-        st16<true>(p + o, pack8<P>(pv[u]));
-        st16<true>(m + o, pack8<P>(mv[u]));
-        st16<true>(v + o, pack8<P>(vv[u]));
+        if constexpr (SR) {
+          st16<true>(p + o, pack8_sr<P>(pv[u], sr.mask & 1, sr, sr.base + o, t, kSrStreamP));
+          st16<true>(m + o, pack8_sr<P>(mv[u], sr.mask & 2, sr, sr.base + o, t, kSrStreamM));
+          st16<true>(v + o, pack8_sr<P>(vv[u], sr.mask & 4, sr, sr.base + o, t, kSrStreamV));
+        } else {
+          st16<true>(p + o, pack8<P>(pv[u]));
+          st16<true>(m + o, pack8<P>(mv[u]));
+          st16<true>(v + o, pack8<P>(vv[u]));
+        }
       }
     }
   }
   for (long o = n8 * 8 + (long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long)gridDim.x * 256) {
     float pv = to_f<P>(p[o]), mv = to_f<P>(m[o]), vv = to_f<P>(v[o]);
     adamw_elem<FAST>(pv, mv, vv, to_f<P>(g[o]), gs, c);
-    p[o] = from_f<P>(pv);
-    m[o] = from_f<P>(mv);
-    v[o] = from_f<P>(vv);
+    if constexpr (SR) {
+      p[o] = from_f_sr<P>(pv, sr.mask & 1, sr, sr.base + o, t, kSrStreamP);
+      m[o] = from_f_sr<P>(mv, sr.mask & 2, sr, sr.base + o, t, kSrStreamM);
+      v[o] = from_f_sr<P>(vv, sr.mask & 4, sr, sr.base + o, t, kSrStreamV);
+    } else {
+      p[o] = from_f<P>(pv);
+      m[o] = from_f<P>(mv);
+      v[o] = from_f<P>(vv);
+    }
   }
 }
 
@@ -270,20 +309,23 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(P* __restrict__ p, fl
 // updated values it already holds: the separate transpose pass re-read the whole model after
 // every update (13.5 GB/step at 7B). Block = one 64 x 64 tile; the updated p tile goes through
 // LDS (padded rows) to 16-B transposed stores. Same math and rounding as adamw_kernel.
-template <typename P, bool FAST, int TILE, bool NT>
+// SR (pra_adamw_t_sr): as adamw16_kernel's; element (r, c) is flat position sr.base + r * cols + c, and
+// the shadow takes the same rounded p, so this stays bitwise equal to the flat kernel plus a transpose.
+template <typename P, bool FAST, int TILE, bool NT, bool SR = false>
 __global__ __launch_bounds__(256) void adamw_t_kernel(P* __restrict__ p, const P* __restrict__ g, P* __restrict__ m,
                                                       P* __restrict__ v, P* __restrict__ pt, int rows, int cols,
                                                       double lr, double b1, double b2, double eps, double wd,
                                                       double bc1, double bc2_sqrt, float gscale,
                                                       const float* __restrict__ gscale_dev,
                                                       const double* __restrict__ hyper_dev,
-                                                      const int* __restrict__ skip_dev) {
+                                                      const int* __restrict__ skip_dev, SrArgs sr) {
   constexpr int CH = TILE / 8;            // 8-element chunks per tile row
   constexpr int PASSES = TILE * CH / 256;  // chunks per thread
   __shared__ uint16_t tile[TILE][TILE + 8];
   if (skip_dev && *skip_dev != 0) return;  // block-uniform, before the barrier below
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
+  [[maybe_unused]] const uint32_t t = SR ? (uint32_t)(sr.step_dev ? *sr.step_dev : sr.step) : 0u;
   const long r0 = (long)blockIdx.y * TILE, c0 = (long)blockIdx.x * TILE;
 #pragma unroll
   for (int k = 0; k < PASSES; ++k) {
@@ -296,11 +338,20 @@ __global__ __launch_bounds__(256) void adamw_t_kernel(P* __restrict__ p, const P
     unpack8<P>(ld16<NT>(v + o), vv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) adamw_elem<FAST>(pv[j], mv[j], vv[j], gv[j], gs, c);
-    st16<NT>(p + o, pack8<P>(pv));
-    st16<NT>(m + o, pack8<P>(mv));
-    st16<NT>(v + o, pack8<P>(vv));
+    if constexpr (SR) {
+      const pra_u32x4 pw = pack8_sr<P>(pv, sr.mask & 1, sr, sr.base + o, t, kSrStreamP);
+      st16<NT>(p + o, pw);
+      st16<NT>(m + o, pack8_sr<P>(mv, sr.mask & 2, sr, sr.base + o, t, kSrStreamM));
+      st16<NT>(v + o, pack8_sr<P>(vv, sr.mask & 4, sr, sr.base + o, t, kSrStreamV));
 #pragma unroll
-    for (int j = 0; j < 8; ++j) tile[r][8 * ch + j] = __builtin_bit_cast(uint16_t, from_f<P>(pv[j]));
+      for (int j = 0; j < 8; ++j) tile[r][8 * ch + j] = (uint16_t)(pw[j >> 1] >> (16 * (j & 1)));
+    } else {
+      st16<NT>(p + o, pack8<P>(pv));
+      st16<NT>(m + o, pack8<P>(mv));
+      st16<NT>(v + o, pack8<P>(vv));
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tile[r][8 * ch + j] = __builtin_bit_cast(uint16_t, from_f<P>(pv[j]));
+    }
   }
   __syncthreads();
 #pragma unroll
@@ -436,12 +487,12 @@ hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* 
       PRA_DISPATCH_16BIT(pdtype, T,
                          hipLaunchKernelGGL((pra::adamw16_kernel<T, true, 2>), dim3(nb), dim3(256), 0, s, (T*)p,
                                             (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                            gscale_dev, hyper_dev, skip_dev));
+                                            gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}));
     } else {
       PRA_DISPATCH_16BIT(pdtype, T,
                          hipLaunchKernelGGL((pra::adamw16_kernel<T, false, 2>), dim3(nb), dim3(256), 0, s,
                                             (T*)p, (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt,
-                                            gscale, gscale_dev, hyper_dev, skip_dev));
+                                            gscale, gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}));
     }
     return hipGetLastError();
   }
@@ -474,7 +525,7 @@ hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void
   PRA_DISPATCH_16BIT(dtype, T,                                                                                  \
                      hipLaunchKernelGGL((pra::adamw_t_kernel<T, FASTV, TILEV, true>), grid, dim3(256), 0, s,    \
                                         (T*)p, (const T*)g, (T*)m, (T*)v, (T*)pt, rows, cols, lr, b1, b2, eps,   \
-                                        wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev))
+                                        wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}))
   if (tile == 128 && fast) {
     PRA_ADAMW_T(true, 128);
   } else if (tile == 128) {
@@ -485,6 +536,63 @@ hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void
     PRA_ADAMW_T(false, 64);
   }
 #undef PRA_ADAMW_T
+  return hipGetLastError();
+}
+
+// Stochastic-rounding AdamW (philox_sr.h): pra_adamw_flat's 16-bit kernel with the tensors in `mask`
+// (bit 0 p, bit 1 exp_avg, bit 2 exp_avg_sq) rounded stochastically; the rest is stored as pra_adamw_flat
+// stores it. base: flat position of p[0] (>= 0, % 8 == 0); step_dev (int32, device), when non-null,
+// replaces step. 16-bit p / g / m / v of one dtype only.
+hipError_t pra_adamw_flat_sr(int dtype, void* p, const void* g, void* m, void* v, long n, double lr, double b1,
+                             double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
+                             const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+                             unsigned long long seed, long long base, int step, const int* step_dev, int mask,
+                             hipStream_t s) {
+  if (base < 0 || base % 8 || mask < 1 || mask > 7 || n < 0) return hipErrorInvalidValue;
+  long nb = (n / 8 + 511) / 512;
+  if (nb > 4096) nb = 4096;
+  if (nb < 1) nb = 1;
+  const pra::SrArgs sr{seed, base, step, step_dev, mask};
+  if (fast) {
+    PRA_DISPATCH_16BIT(dtype, T,
+                       hipLaunchKernelGGL((pra::adamw16_kernel<T, true, 2, true>), dim3(nb), dim3(256), 0, s, (T*)p,
+                                          (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
+                                          gscale_dev, hyper_dev, skip_dev, sr));
+  } else {
+    PRA_DISPATCH_16BIT(dtype, T,
+                       hipLaunchKernelGGL((pra::adamw16_kernel<T, false, 2, true>), dim3(nb), dim3(256), 0, s, (T*)p,
+                                          (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
+                                          gscale_dev, hyper_dev, skip_dev, sr));
+  }
+  return hipGetLastError();
+}
+
+// pra_adamw_t with stochastic rounding; base: flat position of p[0][0]. pt takes the rounded p.
+hipError_t pra_adamw_t_sr(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
+                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
+                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
+                          unsigned long long seed, long long base, int step, const int* step_dev, int mask,
+                          hipStream_t s) {
+  if (rows % 64 || cols % 64 || rows <= 0 || cols <= 0) return hipErrorInvalidValue;
+  if (base < 0 || base % 8 || mask < 1 || mask > 7) return hipErrorInvalidValue;
+  const int tile = (rows % 128 == 0 && cols % 128 == 0) ? 128 : 64;
+  const dim3 grid(cols / tile, rows / tile);
+  const pra::SrArgs sr{seed, base, step, step_dev, mask};
+#define PRA_ADAMW_T_SR(FASTV, TILEV)                                                                               \
+  PRA_DISPATCH_16BIT(dtype, T,                                                                                     \
+                     hipLaunchKernelGGL((pra::adamw_t_kernel<T, FASTV, TILEV, true, true>), grid, dim3(256), 0, s, \
+                                        (T*)p, (const T*)g, (T*)m, (T*)v, (T*)pt, rows, cols, lr, b1, b2, eps, wd,  \
+                                        bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev, sr))
+  if (tile == 128 && fast) {
+    PRA_ADAMW_T_SR(true, 128);
+  } else if (tile == 128) {
+    PRA_ADAMW_T_SR(false, 128);
+  } else if (fast) {
+    PRA_ADAMW_T_SR(true, 64);
+  } else {
+    PRA_ADAMW_T_SR(false, 64);
+  }
+#undef PRA_ADAMW_T_SR
   return hipGetLastError();
 }
 

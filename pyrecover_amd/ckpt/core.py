@@ -190,6 +190,10 @@ def build_state(model, optimizer, lr_scheduler=None, sampler=None, step: int = 0
         # --loss-scale: scale, growth tracker, applied and skipped step counts. Kept here, not in the
         # optimizer state, whose keys stay torch.optim.AdamW's (the reference's)
         ps["loss_scale"] = guard.state_dict()
+    if getattr(optimizer, "sr_mask", 0):
+        # --stochastic-rounding: the mode and the seed of the rounding bits (the bits themselves are a
+        # stateless function of seed, step and position: nothing else to save)
+        ps["stochastic_rounding"] = {"mode": optimizer.sr_mode, "seed": int(optimizer.sr_seed)}
     if extra:
         ps.update(extra)
     state["pyrecover_state"] = ps
@@ -204,6 +208,29 @@ def restore_loss_scale(optimizer, ps: Optional[Dict[str, Any]]):
     sd = (ps or {}).get("loss_scale")
     if guard is not None and sd:
         guard.load_state_dict({k: (v.item() if isinstance(v, torch.Tensor) else v) for k, v in sd.items()})
+
+
+def restore_stochastic_rounding(optimizer, ps: Optional[Dict[str, Any]]):
+    """Restore the --stochastic-rounding seed from a checkpoint's ``pyrecover_state``, so a resumed run
+    draws the bits the uninterrupted run would have. The mode is the command line's: when the
+    checkpoint's differs, the flag wins with a warning. A checkpoint without the entry (written with
+    --stochastic-rounding off) leaves the command line's seed."""
+    sd = (ps or {}).get("stochastic_rounding")
+    if not sd or not hasattr(optimizer, "sr_mask"):
+        return
+    mode = sd["mode"]
+    seed = sd["seed"]
+    seed = int(seed.item() if isinstance(seed, torch.Tensor) else seed)
+    if not optimizer.sr_mask:
+        logger.warning(f"the checkpoint was written with --stochastic-rounding {mode}; this run has it off "
+                       f"and rounds to nearest from here on")
+        return
+    if mode != optimizer.sr_mode:
+        logger.warning(f"--stochastic-rounding {optimizer.sr_mode} differs from the checkpoint's {mode}: "
+                       f"continuing with {optimizer.sr_mode}")
+    if seed != optimizer.sr_seed:
+        logger.info(f"stochastic rounding seed {seed} from the checkpoint (was {optimizer.sr_seed})")
+    optimizer.sr_seed = seed
 
 
 # ------------------------------------------------------------------------------------------

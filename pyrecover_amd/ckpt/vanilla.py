@@ -103,6 +103,7 @@ def load_state_into(model, optimizer, lr_scheduler, sampler, ckpt) -> Tuple[int,
     if optimizer is not None and "optimizer" in ckpt:
         optimizer.load_state_dict(ckpt["optimizer"])
         core.restore_loss_scale(optimizer, ckpt.get("pyrecover_state"))
+        core.restore_stochastic_rounding(optimizer, ckpt.get("pyrecover_state"))
     if lr_scheduler is not None and "lr_scheduler" in ckpt:
         sd = dict(ckpt["lr_scheduler"])
         if hasattr(lr_scheduler, "lr_lambdas"):

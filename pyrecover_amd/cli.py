@@ -131,6 +131,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss-scale-init", type=float, default=65536.0, help="initial scale of --loss-scale dynamic")
     p.add_argument("--loss-scale-growth-interval", type=int, default=2000,
                    help="--loss-scale dynamic: consecutive applied steps before the scale doubles")
+    p.add_argument("--stochastic-rounding", choices=["off", "params", "all"], default="off",
+                   help="round the pure 16-bit AdamW state stochastically instead of to nearest, so updates below "
+                        "half an ulp are applied on average instead of lost: params: the parameters; all: the "
+                        "parameters and both moments. No extra memory; the bits are a stateless function of "
+                        "(--sr-seed, step, position), so resume, replicas, ZeRO-1 and graph replay stay bit-exact. "
+                        "Not with --master-weights fp32 or fp32 models")
+    p.add_argument("--sr-seed", type=int, default=None,
+                   help="seed of the --stochastic-rounding bits (default: --seed; a resumed run takes the checkpoint's)")
     p.add_argument("--no-overlap-optimizer", action="store_true",
                    help="run AdamW after backward instead of per gradient bucket during backward")
     p.add_argument("--resubmit", choices=["none", "requeue", "chain"], default="none",

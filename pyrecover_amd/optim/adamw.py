@@ -17,6 +17,10 @@ the reference's) resumes with the master taken from the loaded parameters.
 :class:`LossScaleGuard` (``--loss-scale``) keeps a loss scale and a per-step "gradient not finite"
 flag in device memory; with :meth:`FlatAdamW.enable_guard` every update kernel skips on that flag
 and the step count is the number of applied updates.
+
+:meth:`FlatAdamW.enable_stochastic_rounding` (``--stochastic-rounding``): the pure 16-bit state is
+rounded stochastically instead of to nearest, with bits that are a stateless function of (seed, step,
+flat position, tensor) (:mod:`pyrecover_amd.optim.sr`, ``csrc/kernels/philox_sr.h``).
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import torch
 
 from .. import _ext
 from ..ops import sched
+from . import sr as _sr
 from ..parallel.flat import FlatParams
 
 # Matrices with a transposed weight shadow (parallel/flat.py) are updated by a tiled AdamW kernel
@@ -181,6 +186,7 @@ class FlatAdamW(torch.optim.AdamW):
         self.grad_scale_dev: Optional[torch.Tensor] = None  # device-side multiplier (clipping)
         # fp32 master + fp32 moments for 16-bit parameters (fp32 / fp64 models already update in place)
         self.master: Optional[torch.Tensor] = None
+        self._master_requested = bool(master_weights)
         if master_weights and flat.data.element_size() == 2:
             self.master = flat.data.float()
         sdt = torch.float32 if self.master is not None else flat.data.dtype
@@ -201,6 +207,42 @@ class FlatAdamW(torch.optim.AdamW):
         self._hyper_ring = []
         self._hyper_slot = 0
         self.guard: Optional[LossScaleGuard] = None  # --loss-scale: device-side skip / scale decisions
+        # --stochastic-rounding: tensor mask (bit 0 p, 1 exp_avg, 2 exp_avg_sq; 0 = round to nearest), seed,
+        # and the device copy of the step number a replayed graph reads (graph mode without a guard)
+        self.sr_mask = 0
+        self.sr_mode = "off"
+        self.sr_seed = 0
+        self.step_dev: Optional[torch.Tensor] = None
+
+    # --- stochastic rounding ------------------------------------------------------------------
+    def enable_stochastic_rounding(self, mode: str = "all", seed: int = 0):
+        """Round the 16-bit state stochastically after every update: ``params`` the parameters only,
+        ``all`` the parameters and both moments. An element's random bits depend only on ``seed``, the
+        step number of the update (the one its bias corrections use), its position in the flat buffer
+        and the tensor, so neither rank, bucket, stream, launch order nor graph replay changes them.
+        The flat layout depends on the world size, so a resume at another world size draws other bits."""
+        if mode not in _sr.MODES:
+            raise ValueError(f"stochastic rounding mode must be one of {sorted(_sr.MODES)}, got {mode!r}")
+        if self._master_requested or self.master is not None:
+            raise ValueError("stochastic rounding rounds the pure 16-bit optimizer state; with master_weights=True "
+                             "the state is fp32 and there is nothing to round: use one or the other")
+        if self.flat.data.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"stochastic rounding needs bf16 or fp16 parameters; {self.flat.data.dtype} state is "
+                             "not rounded after the update")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"stochastic rounding seed must fit 64 unsigned bits, got {seed}")
+        self.sr_mode, self.sr_mask, self.sr_seed = mode, _sr.MODES[mode], seed
+
+    def _sr_kwargs(self, base: int) -> dict:
+        """The SR launches' extra arguments for a slice that starts at flat position ``base``. Step
+        number: the guard's applied count (device), the uploaded copy (graph mode), else the host's."""
+        if self.guard is not None and self.guard.native:
+            step_dev = self.guard.state[LossScaleGuard.APPLIED:LossScaleGuard.APPLIED + 1]
+        else:
+            step_dev = self.step_dev if self.graph_mode else None
+        return {"seed": self.sr_seed, "base": int(base), "step": int(self._step), "step_dev": step_dev,
+                "mask": self.sr_mask}
 
     # --- loss scale / non-finite step guard ---------------------------------------------------
     def enable_guard(self, guard: LossScaleGuard):
@@ -227,19 +269,25 @@ class FlatAdamW(torch.optim.AdamW):
     def _alloc_hyper(self):
         if self.hyper is None:
             self.hyper = torch.zeros(3, dtype=torch.float64, device=self.flat.data.device)
+            self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.flat.data.device)
             # pinned staging ring: a slot is rewritten only after its previous H2D copy completed
-            self._hyper_ring = [(torch.zeros(3, dtype=torch.float64).pin_memory(), torch.cuda.Event())
+            self._hyper_ring = [(torch.zeros(3, dtype=torch.float64).pin_memory(),
+                                 torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event())
                                 for _ in range(4)]
 
     def _upload_hyper(self):
-        """{lr, bc1, bc2_sqrt} -> ``hyper``; guard mode: lr only (the guard kernel writes the rest)."""
+        """{lr, bc1, bc2_sqrt} -> ``hyper``; guard mode: lr only (the guard kernel writes the rest).
+        Stochastic rounding without a guard: the step number -> ``step_dev`` as well."""
         lr, _, _, _, _, bc1, bc2_sqrt = self._coeffs()
-        host, ev = self._hyper_ring[self._hyper_slot]
+        host, host_step, ev = self._hyper_ring[self._hyper_slot]
         self._hyper_slot = (self._hyper_slot + 1) % len(self._hyper_ring)
         ev.synchronize()
         host[0], host[1], host[2] = lr, bc1, bc2_sqrt
         n = 1 if self.guard is not None else 3
         self.hyper[:n].copy_(host[:n], non_blocking=True)
+        if self.sr_mask and self.guard is None:
+            host_step[0] = self._step
+            self.step_dev.copy_(host_step, non_blocking=True)
         ev.record()
 
     # --- captured-step (HIP graph) support ---------------------------------------------------
@@ -288,6 +336,34 @@ class FlatAdamW(torch.optim.AdamW):
         # (fast, skip_dev): a null skip_dev is the kernels' unguarded path
         tail = (FAST_MATH, self.guard.skip_dev) if self.guard is not None else (FAST_MATH,)
         sharded = self._sharded()
+        if self.sr_mask:
+            # stochastic rounding: the same walk as below through the SR launches, every slice with its
+            # flat position, so the bits do not depend on how the range is cut
+            def flat_sr(a, b):
+                if a < b:
+                    C.adamw_flat_sr_(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, *tail, **self._sr_kwargs(a))
+
+            if sharded:
+                flat_sr(lo, hi)
+                return
+            cur, rest = lo, []
+            for o, rows, cols in (f.transposed_in(lo, hi) if FUSED_T else []):
+                n = rows * cols
+                if o + n > hi:
+                    rest.append(o)
+                    continue
+                flat_sr(cur, o)
+                sl = slice(o, o + n)
+                C.adamw_t_sr_(f.data[sl].view(rows, cols), f.grad[sl].view(rows, cols), m[sl].view(rows, cols),
+                              v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, *tail,
+                              **self._sr_kwargs(o))
+                cur = o + n
+            flat_sr(cur, hi)
+            if not FUSED_T:
+                f.refresh_transposed(lo, hi)
+            for o in rest:
+                f.refresh_transposed(o, o + 1)
+            return
         if self.master is not None:
             # fp32 master update, then the transposed shadows of the matrices in range from the
             # rounded parameters (same stream: the next backward sees them; sharded: after the gather)
@@ -494,6 +570,14 @@ class FlatAdamW(torch.optim.AdamW):
         p.addcdiv_(m, denom, value=-(lr / bc1))
         if self.master is not None:
             self.master[lo:hi].copy_(p)
+        if self.sr_mask:
+            # the kernels' rounding rule with the kernels' bits (optim/sr.py): positions lo..hi-1
+            idx = torch.arange(lo, hi, dtype=torch.int64, device=pd.device)
+            for dst, val, stream in ((pd, p, _sr.STREAM_P), (md, m, _sr.STREAM_M), (vd, v, _sr.STREAM_V)):
+                if self.sr_mask >> stream & 1:
+                    val = _sr.stochastic_round(val, dst.dtype, idx, self._step, stream, self.sr_seed)
+                dst.copy_(val)
+            return
         pd.copy_(p)
         md.copy_(m)
         vd.copy_(v)

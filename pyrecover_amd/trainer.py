@@ -277,6 +277,13 @@ def train(args):
     if optimizer.master is not None:
         log_rank0(f"fp32 master weights: {optimizer.master.numel() * 4 / 2**30:.2f} GiB "
                   f"(+ fp32 moments {2 * optimizer.exp_avg.numel() * 4 / 2**30:.2f} GiB)")
+    sr_mode = getattr(args, "stochastic_rounding", "off")
+    if sr_mode != "off":
+        sr_seed = getattr(args, "sr_seed", None)
+        sr_seed = int(args.seed if sr_seed is None else sr_seed) % 2 ** 64
+        optimizer.enable_stochastic_rounding(sr_mode, sr_seed)  # ValueError: fp32 master / fp32 model
+        log_rank0(f"Stochastic rounding: {'parameters' if sr_mode == 'params' else 'parameters and both moments'} "
+                  f"({flat.data.dtype}), seed {sr_seed}; bits from Philox4x32-10 of (seed, step, flat position)")
     guard = None
     if loss_scale != "off":
         dynamic = loss_scale == "dynamic"

@@ -37,6 +37,12 @@ def main():
         "flat": (lambda f: C.adamw_flat_(p.view(-1), g.view(-1), m.view(-1), v.view(-1), fast=f, **hp), 14),
         "t": (lambda f: C.adamw_t_(p, g, m, v, pt, fast=f, **hp), 16),
     }
+    # --stochastic-rounding params / all: the same bytes, one / three Philox calls per 8 elements
+    sr = dict(seed=1234, base=0, step=7)
+    for mode, mask in (("sr_params", 1), ("sr_all", 7)):
+        cases[f"flat_{mode}"] = (lambda f, k=mask: C.adamw_flat_sr_(p.view(-1), g.view(-1), m.view(-1), v.view(-1),
+                                                                   fast=f, mask=k, **hp, **sr), 14)
+        cases[f"t_{mode}"] = (lambda f, k=mask: C.adamw_t_sr_(p, g, m, v, pt, fast=f, mask=k, **hp, **sr), 16)
     out = {}
     for name, (fn, bpe) in cases.items():
         for fast in (False, True):

@@ -32,7 +32,8 @@ def parse_arm(spec):
     steps on packed batches of N equal documents per row (doc_start: document-masked attention); the
     item `clip=MAX_NORM` runs them as --clip-grad does (gradient norm, then the update after the
     backward), `guard=SCALE` as --loss-scale SCALE does (scaled backward, guard kernel, guarded update
-    after the backward)."""
+    after the backward); the item `sr=params|all` rounds the AdamW state stochastically as
+    --stochastic-rounding does (the update stays overlapped)."""
     name, _, body = spec.partition(":")
     sets = []
     for item in filter(None, body.split(";")):
@@ -45,6 +46,9 @@ def parse_arm(spec):
             continue
         if lhs.strip() in ("clip", "guard"):
             sets.append(("mode", lhs.strip(), float(rhs)))
+            continue
+        if lhs.strip() == "sr":
+            sets.append(("sr", "sr", rhs.strip()))
             continue
         mod, _, attr = lhs.strip().rpartition(".")
         if mod in ("attn", "native"):  # attention option / native setter C.<attr>(value), reset to 0 after
@@ -114,7 +118,7 @@ def main():
     def resolve(sets):
         out = []
         for m, k, v in sets:
-            if m in ("attn", "native", "docs", "mode"):
+            if m in ("attn", "native", "docs", "mode", "sr"):
                 continue
             m = opt if m == "opt" else m
             if v == "noupdate":
@@ -134,6 +138,8 @@ def main():
             opt.enable_guard(guard)
         elif "clip" in mode:
             opt.grad_scale_dev = torch.ones(1, device=dev)  # set before the backward: no overlapped update
+        for _, _, v in (s for s in arm[1] if s[0] == "sr"):
+            opt.enable_stochastic_rounding(v, 1234)
         for k, v in natives:
             getattr(_ext.native(), k)(v)
         sets = resolve(arm[1])
@@ -150,6 +156,7 @@ def main():
         finally:
             if mode:  # back to the overlapped, unguarded update with host scalars
                 opt.guard, opt.grad_scale_dev, opt.hyper = None, None, None
+            opt.sr_mode, opt.sr_mask = "off", 0  # back to round-to-nearest
             for k, _ in natives:
                 getattr(_ext.native(), k)(0)
             if prev_attn is not None:
