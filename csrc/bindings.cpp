@@ -395,6 +395,61 @@ void xent_bwd_(at::Tensor logits, const at::Tensor& labels, const at::Tensor& ls
         "xent_bwd");
 }
 
+void check_xent_coefficients(double z_loss, double label_smoothing) {
+  TORCH_CHECK(std::isfinite(z_loss) && z_loss >= 0.0, "xent: z_loss must be finite and >= 0, got ", z_loss);
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "xent: label_smoothing must be in [0, 1), got ",
+              label_smoothing);
+}
+
+// The regularised objective ((1 - eps) nll + eps smooth + z lse^2, mean over the valid rows) and the logit
+// statistics: logits [T, V] (row stride ld), labels [T] -> (lse [T], stats [8] = {objective, n_valid, mean nll,
+// z-loss term, mean smooth, mean lse, max |lse|, 0})
+std::vector<at::Tensor> xent_fwd_reg(const at::Tensor& logits, const at::Tensor& labels, int64_t ignore_index,
+                                     double z_loss, double label_smoothing) {
+  const Range range_("pyrecover::xent_fwd_reg");
+  check_dev(logits, "logits");
+  check_row_major(logits, "logits");
+  check_xent_stride(logits);
+  check_xent_coefficients(z_loss, label_smoothing);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == logits.size(0),
+              "xent: labels must be contiguous int64 [T]");
+  same_dev(logits, labels, "labels");
+  const c10::DeviceGuard guard(logits.device());
+  const int64_t T = logits.size(0);
+  auto fo = logits.options().dtype(at::kFloat);
+  at::Tensor lse = at::empty({T}, fo), rows = at::empty({2, T}, fo), stats = at::empty({8}, fo);
+  check(pra_xent_fwd_reg(dt(logits), logits.data_ptr(), labels.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                         rows.data_ptr<float>(), rows.data_ptr<float>() + T, stats.data_ptr<float>(), T,
+                         logits.size(1), logits.stride(0), ignore_index, z_loss, label_smoothing, stream_of(logits)),
+        "xent_fwd_reg");
+  return {lse, stats};
+}
+
+void xent_bwd_reg_(at::Tensor logits, const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& stats,
+                   const at::Tensor& grad_out, int64_t ignore_index, double z_loss, double label_smoothing) {
+  const Range range_("pyrecover::xent_bwd_reg");
+  check_dev(logits, "logits");
+  check_row_major(logits, "logits");
+  check_xent_stride(logits);
+  check_xent_coefficients(z_loss, label_smoothing);
+  TORCH_CHECK(grad_out.scalar_type() == at::kFloat && grad_out.numel() == 1 && grad_out.is_cuda(),
+              "xent_bwd: grad_out must be a 1-element fp32 GPU tensor");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_contiguous() && labels.numel() == logits.size(0),
+              "xent_bwd: labels");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == logits.size(0) && lse.is_contiguous() &&
+              stats.numel() == 8 && stats.scalar_type() == at::kFloat && stats.is_contiguous(),
+              "xent_bwd_reg: lse must be fp32 [T] and stats fp32 [8]");
+  same_dev(logits, labels, "labels");
+  same_dev(logits, lse, "lse");
+  same_dev(logits, stats, "stats");
+  same_dev(logits, grad_out, "grad_out");
+  const c10::DeviceGuard guard(logits.device());
+  check(pra_xent_bwd_reg(dt(logits), logits.data_ptr(), labels.data_ptr<int64_t>(), lse.data_ptr<float>(),
+                         stats.data_ptr<float>(), grad_out.data_ptr<float>(), logits.size(0), logits.size(1),
+                         logits.stride(0), ignore_index, z_loss, label_smoothing, stream_of(logits)),
+        "xent_bwd_reg");
+}
+
 // The AdamW kernels' optional skip flag: int32[>=1] on p's device (non-zero: the launch does nothing).
 static const int* skip_flag(const at::Tensor& p, const c10::optional<at::Tensor>& skip_dev) {
   if (!skip_dev.has_value()) return nullptr;
@@ -1050,6 +1105,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("embedding_bwd", &embedding_bwd);
   m.def("xent_fwd", &xent_fwd);
   m.def("xent_bwd_", &xent_bwd_);
+  m.def("xent_fwd_reg", &xent_fwd_reg);
+  m.def("xent_bwd_reg_", &xent_bwd_reg_);
   namespace py = pybind11;
   m.def("adamw_flat_", &adamw_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),

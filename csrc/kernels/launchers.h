@@ -59,6 +59,13 @@ hipError_t pra_xent_fwd(int dtype, const void* logits, const int64_t* labels, fl
                         float* stats, long T, long V, long ld, long ignore_index, hipStream_t s);
 hipError_t pra_xent_bwd(int dtype, void* logits, const int64_t* labels, const float* lse, const float* stats,
                         const float* grad_out, long T, long V, long ld, long ignore_index, hipStream_t s);
+// regularised objective (z-loss, label smoothing) and logit telemetry; stats is float[8]
+hipError_t pra_xent_fwd_reg(int dtype, const void* logits, const int64_t* labels, float* lse, float* nll_row,
+                            float* smooth_row, float* stats, long T, long V, long ld, long ignore_index, double z_loss,
+                            double label_smoothing, hipStream_t s);
+hipError_t pra_xent_bwd_reg(int dtype, void* logits, const int64_t* labels, const float* lse, const float* stats,
+                            const float* grad_out, long T, long V, long ld, long ignore_index, double z_loss,
+                            double label_smoothing, hipStream_t s);
 
 hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n, double lr,
                           double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,

@@ -194,6 +194,9 @@ def build_state(model, optimizer, lr_scheduler=None, sampler=None, step: int = 0
         # --stochastic-rounding: the mode and the seed of the rounding bits (the bits themselves are a
         # stateless function of seed, step and position: nothing else to save)
         ps["stochastic_rounding"] = {"mode": optimizer.sr_mode, "seed": int(optimizer.sr_seed)}
+    if getattr(m, "loss_regularised", False):
+        # --z-loss / --label-smoothing / --logit-stats: what the run's objective was (no key with the plain loss)
+        ps["loss"] = {"z_loss": float(m.z_loss), "label_smoothing": float(m.label_smoothing)}
     if extra:
         ps.update(extra)
     state["pyrecover_state"] = ps
@@ -208,6 +211,24 @@ def restore_loss_scale(optimizer, ps: Optional[Dict[str, Any]]):
     sd = (ps or {}).get("loss_scale")
     if guard is not None and sd:
         guard.load_state_dict({k: (v.item() if isinstance(v, torch.Tensor) else v) for k, v in sd.items()})
+
+
+def warn_loss_options_change(model, ps: Optional[Dict[str, Any]]) -> List[str]:
+    """Warn when the checkpoint was written under another objective (``pyrecover_state.loss``: --z-loss,
+    --label-smoothing; no entry means the plain loss). The command line wins: the run continues with
+    its own values."""
+    sd = (ps or {}).get("loss") or {}
+    diffs = []
+    for key, flag in (("z_loss", "--z-loss"), ("label_smoothing", "--label-smoothing")):
+        was = sd.get(key, 0.0)
+        was = float(was.item() if isinstance(was, torch.Tensor) else was)
+        now = float(getattr(model, key, 0.0))
+        if was != now:
+            diffs.append(f"{flag} {now:g} (checkpoint: {was:g})")
+    if diffs:
+        logger.warning("the checkpoint was written with another training objective; continuing with the command "
+                       "line's: " + "; ".join(diffs))
+    return diffs
 
 
 def restore_stochastic_rounding(optimizer, ps: Optional[Dict[str, Any]]):

@@ -116,6 +116,8 @@ def save_ckpt_distributed(model, optimizer, lr_scheduler=None, sampler=None, ste
         dstate["pyrecover_state"]["loss_scale"] = state["pyrecover_state"]["loss_scale"]
     if "stochastic_rounding" in state["pyrecover_state"]:
         dstate["pyrecover_state"]["stochastic_rounding"] = state["pyrecover_state"]["stochastic_rounding"]
+    if "loss" in state["pyrecover_state"]:
+        dstate["pyrecover_state"]["loss"] = state["pyrecover_state"]["loss"]
     if rngs is not None:
         dstate["pyrecover_state"]["rng_per_rank"] = {str(r): st for r, st in enumerate(rngs)}
     items = flatten_state(dstate)

@@ -139,6 +139,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "Not with --master-weights fp32 or fp32 models")
     p.add_argument("--sr-seed", type=int, default=None,
                    help="seed of the --stochastic-rounding bits (default: --seed; a resumed run takes the checkpoint's)")
+    p.add_argument("--z-loss", type=_z_loss, default=0.0, metavar="FLOAT",
+                   help="auxiliary z-loss coefficient: adds z * logsumexp(logits)^2 per token to the objective (keeps "
+                        "the output logits' log-partition from drifting in 16-bit training; 1e-4 is usual). Computed in "
+                        "the fused cross-entropy kernels. The logged loss stays the plain cross-entropy")
+    p.add_argument("--label-smoothing", type=_label_smoothing, default=0.0, metavar="FLOAT",
+                   help="label smoothing in [0, 1), as torch.nn.functional.cross_entropy(label_smoothing=), in the fused "
+                        "cross-entropy kernels. The logged loss stays the plain cross-entropy")
+    p.add_argument("--logit-stats", action="store_true",
+                   help="log the output logits' log-partition statistics (lse_mean, lse_absmax in --metrics-jsonl) with "
+                        "both coefficients zero; --z-loss and --label-smoothing log them anyway")
     p.add_argument("--no-overlap-optimizer", action="store_true",
                    help="run AdamW after backward instead of per gradient bucket during backward")
     p.add_argument("--resubmit", choices=["none", "requeue", "chain"], default="none",
@@ -171,6 +181,28 @@ def _loss_scale(v: str):
         f = -1.0
     if not (0.0 < f < float("inf")):
         raise argparse.ArgumentTypeError(f"{v!r}: expected off, dynamic or a positive number")
+    return f
+
+
+def _z_loss(v: str):
+    """--z-loss: a finite float >= 0."""
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if not (0.0 <= f < float("inf")):
+        raise argparse.ArgumentTypeError(f"{v!r}: expected a finite number >= 0")
+    return f
+
+
+def _label_smoothing(v: str):
+    """--label-smoothing: a float in [0, 1)."""
+    try:
+        f = float(v)
+    except ValueError:
+        f = -1.0
+    if not (0.0 <= f < 1.0):
+        raise argparse.ArgumentTypeError(f"{v!r}: expected a number in [0, 1)")
     return f
 
 

@@ -15,6 +15,9 @@ What changes per step without re-capture:
 * with ``--loss-scale`` the loss scale, the decision to skip a non-finite step and the bias
   corrections live in device memory (optim.adamw.LossScaleGuard, run in ``pre_step``): the captured
   kernels read them, so a replay skips, halves or doubles without the host knowing;
+* the model's loss options (``--z-loss``, ``--label-smoothing``, ``--logit-stats``) are constants of the
+  capture; the head's statistics land in one static tensor (``StepGraph.stats``) that every replay
+  refreshes;
 * checkpoint snapshot fences are applied to the stream *before* the replay (a captured graph
   cannot wait on an event recorded outside it), so a step never overtakes an in-flight
   checkpoint copy.
@@ -62,6 +65,7 @@ class StepGraph:
         self.static_y = None
         self.static_ds = None  # doc_start of a packed batch (int32), or None
         self.loss = None
+        self.stats = None  # the regularised head's statistics (static fp32 [8]), or None with the plain loss
         self.replays = 0
 
     @property
@@ -73,6 +77,8 @@ class StepGraph:
             loss = self.model(self.static_x, labels=self.static_y, doc_start=self.static_ds)
         else:
             loss = self.model(self.static_x, labels=self.static_y)
+        self.stats = getattr(self.model, "last_loss_stats", None) if getattr(self.model, "loss_regularised",
+                                                                             False) else None
         seed = self.loss_scale() if callable(self.loss_scale) else self.loss_scale
         (loss if seed is None else loss * seed).backward()
         if self.reducer is not None:

@@ -153,6 +153,14 @@ class Transformer(nn.Module):
         self.register_buffer("rope_tab", rope_table(self.freqs_cis), persistent=False)
         self.flat: Optional[FlatParams] = None
         self.activation_checkpointing = False  # train.py --activation-checkpointing
+        # loss options, set by the trainer (--z-loss, --label-smoothing, --logit-stats): plain attributes,
+        # not parameters, buffers or state_dict entries. With any of them on, the loss forward returns the
+        # regularised objective and leaves the head's statistics in last_loss_stats (fp32 device tensor
+        # [8], ops/reference.py cross_entropy_reg_ref; no host sync)
+        self.z_loss = 0.0
+        self.label_smoothing = 0.0
+        self.logit_stats = False
+        self.last_loss_stats = None
 
     def _precompute_freqs_cis(self) -> torch.Tensor:
         a = self.model_args
@@ -340,10 +348,20 @@ class Transformer(nn.Module):
         document is computed exactly as if it stood alone in a row of its own."""
         nf = self._trunk(tokens, doc_start)
         W = self.output.weight
+        if labels is not None and self.loss_regularised:
+            loss, self.last_loss_stats = F.linear_cross_entropy_stats(
+                nf, self._weight([W]), labels, self._slot([W]), W, ignore_index, w_t=self._weight_t([W]),
+                z_loss=self.z_loss, label_smoothing=self.label_smoothing)
+            return loss
         if labels is not None:
             return F.linear_cross_entropy(nf, self._weight([W]), labels, self._slot([W]), W, ignore_index,
                                           w_t=self._weight_t([W]))
         return torch.nn.functional.linear(nf, W)
+
+    @property
+    def loss_regularised(self) -> bool:
+        """Whether the loss forward runs the regularised head (objective + statistics)."""
+        return bool(self.z_loss > 0 or self.label_smoothing > 0 or self.logit_stats)
 
     # ----------------------------------------------------------------------------------
     def num_params(self, exclude_embedding: bool = False) -> int:

@@ -8,12 +8,14 @@ from .fused import (  # noqa: F401
     embedding,
     flash_attention,
     linear_cross_entropy,
+    linear_cross_entropy_stats,
     swiglu_mlp,
 )
 from .reference import (  # noqa: F401
     apply_rotary_emb_ref,
     attention_ref,
     cross_entropy_ref,
+    cross_entropy_reg_ref,
     precompute_freqs_cis,
     rmsnorm_ref,
     rope_table,

@@ -744,7 +744,83 @@ class _LinearCrossEntropy(torch.autograd.Function):
         return dh.view(ctx.hshape), None, None, None, None, None, None
 
 
-def linear_cross_entropy(h, w_out, labels, slot, weight_param, ignore_index: int = -100, w_t=None):
+class _LinearCrossEntropyReg(torch.autograd.Function):
+    """The head with the regularised objective ((1 - eps) nll + eps smooth + z lse^2, mean over the
+    valid rows; ops/reference.py cross_entropy_reg_ref) and the logit statistics, in the same two
+    passes over the 16-bit logits as :class:`_LinearCrossEntropy` (csrc/kernels/xent.hip, the *_reg
+    kernels). Returns (objective, stats [8]); stats is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, w_out, labels, slot, ignore_index, w_t, weight_param, z_loss, label_smoothing):
+        ctx.w_t = w_t
+        h2 = h.reshape(-1, h.shape[-1])
+        lab = labels.reshape(-1).contiguous()
+        logits = _mm_nt(h2, w_out, "head")
+        if _ext.hip(logits):
+            lse, stats = _ext.require_for(logits).xent_fwd_reg(logits, lab, ignore_index, z_loss, label_smoothing)
+            loss = stats[0]
+        else:
+            lse = torch.logsumexp(ref.up(logits), dim=-1)
+            loss, stats = ref.cross_entropy_reg_ref(logits, lab, ignore_index, z_loss, label_smoothing)
+            loss = loss.detach()
+        ctx.save_for_backward(h2, logits, lab, lse, w_out, stats)
+        ctx.slot = slot
+        ctx.ignore_index = ignore_index
+        ctx.coef = (z_loss, label_smoothing)
+        ctx.hshape = h.shape
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats):
+        h2, logits, lab, lse, w_out, stats = ctx.saved_tensors
+        z, eps = ctx.coef
+        if _ext.hip(logits):
+            g = dloss.reshape(1).float().contiguous()
+            _ext.require_for(logits).xent_bwd_reg_(logits, lab, lse, stats, g, ctx.ignore_index, z, eps)
+            dlogits = logits
+        else:
+            V = logits.shape[-1]
+            valid = lab.ne(ctx.ignore_index) & lab.ge(0) & lab.lt(V)
+            n = valid.sum().clamp_min(1)
+            # softmax as the plain head's branch takes it: z = 0, eps = 0 then gives that branch's values
+            p = torch.softmax(ref.up(logits), dim=-1) * (1.0 + 2.0 * z * lse)[:, None] - eps / V
+            p[torch.arange(lab.numel(), device=p.device), lab.clamp(0, V - 1)] -= (1.0 - eps)
+            p = p * valid.to(p.dtype).unsqueeze(1) * (dloss.to(p.dtype) / n)
+            dlogits = p.to(logits.dtype)
+        dh = _mm_dgrad(dlogits, w_out, ctx.w_t, "head_d")
+        _wgrad_into(ctx.slot, dlogits, h2, tuple(w_out.shape), "head")
+        return dh.view(ctx.hshape), None, None, None, None, None, None, None, None
+
+
+def _check_loss_options(z_loss, label_smoothing):
+    z_loss, label_smoothing = float(z_loss), float(label_smoothing)
+    if not (math.isfinite(z_loss) and z_loss >= 0.0):
+        raise ValueError(f"z_loss must be finite and >= 0, got {z_loss}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+    return z_loss, label_smoothing
+
+
+def linear_cross_entropy_stats(h, w_out, labels, slot, weight_param, ignore_index: int = -100, w_t=None,
+                               z_loss: float = 0.0, label_smoothing: float = 0.0):
+    """(objective, stats): the regularised head. stats is the fp32 device tensor [8] = {objective, n,
+    plain cross-entropy, z-loss term, mean smooth, mean lse, max |lse|, 0} of this forward (see
+    ops/reference.py cross_entropy_reg_ref); reading it needs no sync until the caller asks for one."""
+    z_loss, label_smoothing = _check_loss_options(z_loss, label_smoothing)
+    return _LinearCrossEntropyReg.apply(h, w_out, labels, slot, ignore_index, w_t, weight_param, z_loss,
+                                        label_smoothing)
+
+
+def linear_cross_entropy(h, w_out, labels, slot, weight_param, ignore_index: int = -100, w_t=None,
+                         z_loss: float = 0.0, label_smoothing: float = 0.0, logit_stats: bool = False):
+    """The head's loss. With ``z_loss`` > 0, ``label_smoothing`` > 0 or ``logit_stats`` the regularised
+    kernels run and the objective is returned (:func:`linear_cross_entropy_stats` also hands out the
+    statistics); otherwise exactly the plain mean NLL on the plain kernels."""
+    if z_loss > 0 or label_smoothing > 0 or logit_stats:
+        return linear_cross_entropy_stats(h, w_out, labels, slot, weight_param, ignore_index, w_t, z_loss,
+                                          label_smoothing)[0]
+    _check_loss_options(z_loss, label_smoothing)
     return _LinearCrossEntropy.apply(h, w_out, labels, slot, ignore_index, w_t, weight_param)
 
 

@@ -168,3 +168,38 @@ def cross_entropy_ref(logits, labels, ignore_index: int = -100):
     loss = F.cross_entropy(up(logits.flatten(0, -2)), labels.flatten(), reduction="sum",
                            ignore_index=ignore_index)
     return loss / n
+
+
+def cross_entropy_reg_ref(logits, labels, ignore_index: int = -100, z_loss: float = 0.0, label_smoothing: float = 0.0):
+    """The regularised objective and its statistics in torch math (the opmath of ``logits``).
+
+    Per valid row (label in [0, V) and not ``ignore_index``), lse = logsumexp(x): nll = lse - x[label],
+    smooth = lse - mean(x), zterm = z_loss * lse^2. With n valid rows,
+    objective = ((1 - eps) * sum nll + eps * sum smooth + sum zterm) / n, which at z_loss = 0 is
+    ``F.cross_entropy(label_smoothing=eps, reduction="sum") / n``.
+
+    Returns (objective, stats): stats [8] = {objective, n, sum nll / n (the plain cross-entropy),
+    sum zterm / n, sum smooth / n, mean lse, max |lse| (both over the valid rows), 0}. As in the HIP
+    kernels, sum smooth / n is only formed with label_smoothing > 0 (else that entry is 0, NaN for
+    n = 0). Differentiable through ``objective``; stats is detached."""
+    x = up(logits.flatten(0, -2))
+    lab = labels.flatten()
+    V = x.shape[-1]
+    valid = lab.ne(ignore_index) & lab.ge(0) & lab.lt(V)
+    n = valid.sum()
+    nf = n.to(x.dtype)
+    lse = torch.logsumexp(x, dim=-1)
+    zero = torch.zeros_like(lse)
+    nll = torch.where(valid, lse - x.gather(1, lab.clamp(0, V - 1)[:, None])[:, 0], zero)
+    lv = torch.where(valid, lse, zero)
+    ce = nll.sum() / nf
+    zt = z_loss * (lv.pow(2).sum() / nf)
+    if label_smoothing > 0:
+        sv = torch.where(valid, lse - x.mean(-1), zero).sum() / nf
+    else:
+        sv = zero.sum() / nf
+    obj = (1.0 - label_smoothing) * ce + label_smoothing * sv + zt
+    with torch.no_grad():
+        stats = torch.stack([obj, nf, ce, zt, sv, lv.sum() / nf, lv.abs().max() if lv.numel() else zero.sum(),
+                             torch.zeros_like(nf)]).detach()
+    return obj, stats

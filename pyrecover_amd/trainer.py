@@ -226,6 +226,14 @@ def train(args):
     with set_default_dtype(model_dtype), torch.device(device):
         model = Transformer(model_config)
     model.activation_checkpointing = bool(getattr(args, "activation_checkpointing", False))
+    model.z_loss = float(getattr(args, "z_loss", 0.0) or 0.0)
+    model.label_smoothing = float(getattr(args, "label_smoothing", 0.0) or 0.0)
+    model.logit_stats = bool(getattr(args, "logit_stats", False))
+    loss_reg = model.loss_regularised
+    if loss_reg:
+        log_rank0(f"Objective: cross-entropy with label smoothing {model.label_smoothing:g} + z-loss "
+                  f"{model.z_loss:g} * logsumexp^2, in the fused loss kernels; the logged loss stays the plain "
+                  f"cross-entropy, the objective and the logit statistics go to the log line and --metrics-jsonl")
     shard = _use_shard_optimizer(getattr(args, "shard_optimizer", "off"), world_size if is_dist else 1, model,
                                  local_batch_size * seq_len,
                                  device.type == "cuda" and model_dtype in (torch.bfloat16, torch.float16))
@@ -480,6 +488,7 @@ def train(args):
     if world_size > 1:
         print(f"[Rank {rank}] Starting training on {device}", flush=True)
     loss = None
+    loss_stats = None  # the regularised head's statistics of the last step (device tensor [8])
     while train_step < args.training_steps:
         train_step += 1
         if cost is not None:
@@ -537,6 +546,7 @@ def train(args):
             poison.fill_(float("nan") if on else 0.0)
         if step_graph is not None and eager_steps_this_run >= args.compile_warmup_steps:
             loss = step_graph.step(*micro[0])  # fences the snapshot before the replay
+            loss_stats = step_graph.stats
         else:
             if comm_timer is not None:
                 comm_timer.begin_step()
@@ -553,14 +563,24 @@ def train(args):
                 sd = backward_seed()
                 (lm if sd is None else lm * sd).backward()  # the logged loss stays unscaled
                 loss = lm.detach() if loss is None else loss + lm.detach()
+                if loss_reg:
+                    st = model.last_loss_stats
+                    loss_stats = st if m == 0 else torch.cat([loss_stats[:6] + st[:6],
+                                                              torch.maximum(loss_stats[6:], st[6:])])
             if accum > 1:
                 loss = loss / accum
+                if loss_reg:  # the mean of the micro-batches' statistics, the maximum of lse_absmax
+                    loss_stats = torch.cat([loss_stats[:6] / accum, loss_stats[6:]])
             if reducer is not None:
                 reducer.finish()
             pre_update()
             ckcore.fence_all()  # an async snapshot must land before parameters change
             optimizer.step()
             eager_steps_this_run += 1
+        if loss_reg:
+            # "loss" stays the plain cross-entropy (comparable with unregularised runs; exp(loss) is the
+            # perplexity); the objective is reported beside it
+            loss = loss_stats[2]
         lr_scheduler.step()
 
         if csv_writer is not None:
@@ -570,7 +590,11 @@ def train(args):
         if train_step == 1 or train_step % args.logging_frequency == 0:
             # sync first: the host runs ahead of the GPU, so an unsynchronized clock would count
             # queued-but-unexecuted steps (the reference reads the clock before its .item())
-            lval = loss.item()
+            if loss_reg:
+                sv = loss_stats.tolist()  # the log step's one sync reads all eight
+                lval = sv[2]
+            else:
+                lval = loss.item()
             gstate = guard.read() if guard is not None else None  # the host has just synchronized
             time_delta = time.perf_counter() - time_last_log
             tps = ntokens_since_last_log / time_delta
@@ -588,6 +612,10 @@ def train(args):
                        "nonpad_fraction": nonpad_since_last_log / max(rows_since_last_log * seq_len, 1),
                        "time": time.time()}
                 rec.update(_diagnostics(step_timer, device, comm_timer, world_size, ckpt_window, stopper))
+                if loss_reg:
+                    rec.update(objective=sv[0], z_loss_term=sv[3],
+                               smoothing_term=model.label_smoothing * (sv[4] - sv[2]) if model.label_smoothing > 0
+                               else 0.0, lse_mean=sv[5], lse_absmax=sv[6])
                 if gstate is not None:
                     gn = gstate["grad_norm"]  # of the last step; not finite (null) when it was skipped
                     rec.update(loss_scale=gstate["scale"], skipped_steps=gstate["skipped_total"],
@@ -596,6 +624,9 @@ def train(args):
                 metrics_f.flush()
             elif comm_timer is not None:
                 comm_timer.steps.clear()
+            if loss_reg:
+                log_rank0(f"Objective: {sv[0]:.4f} | z-loss term: {sv[3]:.3g} | lse mean: {sv[5]:.3f} | "
+                          f"lse |max|: {sv[6]:.3f}")
             if gstate is not None:
                 log_rank0(f"Loss scale: {gstate['scale']:g} | Skipped steps: {gstate['skipped_total']} | "
                           f"Grad norm: {gstate['grad_norm']:.4g}")

@@ -33,7 +33,8 @@ def parse_arm(spec):
     item `clip=MAX_NORM` runs them as --clip-grad does (gradient norm, then the update after the
     backward), `guard=SCALE` as --loss-scale SCALE does (scaled backward, guard kernel, guarded update
     after the backward); the item `sr=params|all` rounds the AdamW state stochastically as
-    --stochastic-rounding does (the update stays overlapped)."""
+    --stochastic-rounding does (the update stays overlapped); the item `zloss=Z` runs the head with
+    the z-loss coefficient Z as --z-loss does (the regularised cross-entropy kernels)."""
     name, _, body = spec.partition(":")
     sets = []
     for item in filter(None, body.split(";")):
@@ -49,6 +50,9 @@ def parse_arm(spec):
             continue
         if lhs.strip() == "sr":
             sets.append(("sr", "sr", rhs.strip()))
+            continue
+        if lhs.strip() == "zloss":
+            sets.append(("zloss", "zloss", float(rhs)))
             continue
         mod, _, attr = lhs.strip().rpartition(".")
         if mod in ("attn", "native"):  # attention option / native setter C.<attr>(value), reset to 0 after
@@ -118,7 +122,7 @@ def main():
     def resolve(sets):
         out = []
         for m, k, v in sets:
-            if m in ("attn", "native", "docs", "mode", "sr"):
+            if m in ("attn", "native", "docs", "mode", "sr", "zloss"):
                 continue
             m = opt if m == "opt" else m
             if v == "noupdate":
@@ -140,6 +144,7 @@ def main():
             opt.grad_scale_dev = torch.ones(1, device=dev)  # set before the backward: no overlapped update
         for _, _, v in (s for s in arm[1] if s[0] == "sr"):
             opt.enable_stochastic_rounding(v, 1234)
+        model.z_loss = max([v for m, _, v in arm[1] if m == "zloss"] or [0.0])
         for k, v in natives:
             getattr(_ext.native(), k)(v)
         sets = resolve(arm[1])
@@ -157,6 +162,7 @@ def main():
             if mode:  # back to the overlapped, unguarded update with host scalars
                 opt.guard, opt.grad_scale_dev, opt.hyper = None, None, None
             opt.sr_mode, opt.sr_mask = "off", 0  # back to round-to-nearest
+            model.z_loss = 0.0
             for k, _ in natives:
                 getattr(_ext.native(), k)(0)
             if prev_attn is not None:
