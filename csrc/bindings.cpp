@@ -988,6 +988,80 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
   return {o, lse};
 }
 
+// ---------------------------------------------------------------------------------------
+// KV-cache generation (csrc/kernels/attention_decode.hip)
+void check_decode_common(const at::Tensor& ref, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& kv_len,
+                         int64_t B, const char* op) {
+  TORCH_CHECK(ref.scalar_type() == at::kBFloat16 || ref.scalar_type() == at::kHalf, op,
+              ": the HIP kernels take bf16 or fp16 (got ", ref.scalar_type(),
+              "); other dtypes run the torch math of pyrecover_amd.ops.reference");
+  same_dev(ref, kc, "k_cache");
+  same_dev(ref, vc, "v_cache");
+  same_dev(ref, kv_len, "kv_len");
+  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(1) > 0 && kc.size(2) > 0, op,
+              ": k_cache must be [B, cap, Hkv, D] with B = ", B, ", got ", kc.sizes());
+  TORCH_CHECK(vc.sizes() == kc.sizes(), op, ": v_cache must have k_cache's shape");
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), op, ": the caches must be contiguous");
+  TORCH_CHECK(kc.scalar_type() == ref.scalar_type() && vc.scalar_type() == ref.scalar_type(), op,
+              ": the caches must have the query's dtype");
+  TORCH_CHECK(kc.size(3) == 64 || kc.size(3) == 128, op, ": head_dim must be 64 or 128");
+  TORCH_CHECK(kc.size(1) <= (int64_t)INT32_MAX / 2 && kc.size(2) <= 65535 && B > 0 && B <= 65535, op, ": bad shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0,
+              op, ": the caches must be 16-B aligned");
+  TORCH_CHECK(kv_len.scalar_type() == at::kInt && kv_len.dim() == 1 && kv_len.size(0) == B && kv_len.is_contiguous(),
+              op, ": kv_len must be contiguous int32 [B]");
+}
+
+// qkv [B, (Hq + 2 Hkv) D] (rows of the fused QKV activation): q rotated in place at position
+// clamp(kv_len[b], 0, cap - 1), rotated k and plain v written into that row of the caches.
+void rope_append_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_len, at::Tensor k_cache,
+                  at::Tensor v_cache) {
+  const Range range_("pyrecover::rope_append");
+  check_dev(qkv, "qkv");
+  check_row_major(qkv, "rope_append qkv");
+  const int64_t B = qkv.size(0);
+  check_decode_common(qkv, k_cache, v_cache, kv_len, B, "rope_append");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(qkv.size(1) % D == 0 && qkv.size(1) / D > 2 * Hkv && (qkv.size(1) / D - 2 * Hkv) % Hkv == 0,
+              "rope_append: qkv must be [B, (Hq + 2 Hkv) D] with Hq a multiple of Hkv, got ", qkv.sizes());
+  TORCH_CHECK(qkv.stride(0) % 8 == 0, "rope_append: the qkv row stride must be a multiple of 8 elements");
+  const int64_t Hq = qkv.size(1) / D - 2 * Hkv;
+  same_dev(qkv, tab, "rope table");
+  TORCH_CHECK(tab.scalar_type() == at::kFloat && tab.is_contiguous() && tab.dim() == 3 && tab.size(0) >= cap &&
+                  tab.size(1) == D / 2 && tab.size(2) == 2,
+              "rope_append: table must be contiguous fp32 [>= cap, D/2, 2]");
+  const c10::DeviceGuard guard(qkv.device());
+  check(pra_rope_append(dt(qkv), qkv.data_ptr(), tab.data_ptr(), kv_len.data_ptr<int>(), k_cache.data_ptr(),
+                        v_cache.data_ptr(), (int)B, qkv.stride(0), (int)Hq, (int)Hkv, (int)D, (int)cap, stream_of(qkv)),
+        "rope_append");
+}
+
+// q [B, Hq, D] (rows may be strided views of the QKV activation), caches [B, cap, Hkv, D], kv_len int32 [B]
+// on the device -> (o [B, Hq, D], lse fp32 [B, Hq]).
+std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                    const at::Tensor& kv_len, double scale) {
+  const Range range_("pyrecover::attn_decode");
+  check_dev(q, "q");
+  TORCH_CHECK(q.dim() == 3, "attn_decode: q must be [B, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  check_decode_common(q, k_cache, v_cache, kv_len, B, "attn_decode");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "attn_decode: q and the caches disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_decode: n_heads must be a multiple of n_kv_heads");
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_decode: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, Hq}, q.options().dtype(at::kFloat));
+  at::Tensor ws = at::empty({pra_attn_decode_ws_floats((int)B, (int)Hq, (int)D, (int)cap)},
+                            q.options().dtype(at::kFloat));
+  check(pra_attn_decode(dt(q), qc.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), kv_len.data_ptr<int>(),
+                        o.data_ptr(), lse.data_ptr<float>(), ws.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv, (int)D,
+                        (int)cap, (float)scale, stream_of(q)),
+        "attn_decode");
+  return {o, lse};
+}
+
 // Writes dq/dk/dv into caller-provided [B,S,H,D] views (e.g. slices of a fused dQKV buffer).
 void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& dout, const at::Tensor& lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
@@ -1150,6 +1224,11 @@ PYBIND11_MODULE(_C, m) {
         pybind11::arg("dout"), pybind11::arg("lse"), pybind11::arg("dq"), pybind11::arg("dk"), pybind11::arg("dv"),
         pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("rope_tab") = pybind11::none(),
         pybind11::arg("mid_event") = 0, pybind11::arg("doc_start") = pybind11::none());
+  m.def("rope_append_", &rope_append_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_cache"),
+        py::arg("v_cache"));
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
+        py::arg("scale"));
+  m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
   m.def("attn_set_order", [](int fwd, int dq, int dkdv) { pra_attn_set_order(fwd, dq, dkdv); },
         "block order of the attention grids: 0 = heavy tiles first, G > 0 = XCD-grouped with G heads per group, "
         "-1 = by shape", pybind11::arg("fwd"), pybind11::arg("dq"), pybind11::arg("dkdv"));

@@ -159,4 +159,18 @@ hipError_t pra_attn_bwd_f32(const float* q, const float* k, const float* v, cons
                             const float* lse, float* delta, float* dq, float* dk, float* dv, int B, int S, int Hq,
                             int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
                             long lddv, float scale, int causal, int skv, hipStream_t st);
+
+// KV-cache generation (attention_decode.hip), bf16 / fp16. Caches are [B][cap][Hkv][D] contiguous;
+// kv_len is int32 [B] on the device and is clamped by the kernels (no host copy is ever read).
+// rope_append: qkv [B][ld] = q | k | v of the new tokens; rotates q in place, writes rotated k and
+// plain v into cache row clamp(kv_len[b], 0, cap - 1). tab: float2 [>= cap][D/2].
+hipError_t pra_rope_append(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
+                           int B, long ld, int Hq, int Hkv, int D, int cap, hipStream_t s);
+// q, o [B][Hq][D] contiguous, lse fp32 [B][Hq]; sequence b attends to keys 0 .. clamp(kv_len[b], 0, cap) - 1.
+// D 64 or 128. ws: pra_attn_decode_ws_floats fp32 words. pra_attn_decode_chunk: keys per chunk.
+hipError_t pra_attn_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, const int* kv_len,
+                           void* o, float* lse, float* ws, int B, int Hq, int Hkv, int D, int cap, float scale,
+                           hipStream_t s);
+long pra_attn_decode_ws_floats(int B, int Hq, int D, int cap);
+int pra_attn_decode_chunk();
 }

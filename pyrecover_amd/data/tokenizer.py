@@ -28,6 +28,11 @@ class ByteTokenizer:
     def encode(self, text: str) -> List[int]:
         return [self.bos_token_id] + [b + 3 for b in text.encode("utf-8", errors="replace")]
 
+    def decode(self, ids) -> str:
+        """Inverse of :meth:`encode`: ids 3..258 back to UTF-8 bytes; ids outside the byte range (pad, bos,
+        eos, anything above 258 or below 0) decode to nothing. Invalid UTF-8 becomes U+FFFD."""
+        return bytes(int(i) - 3 for i in ids if 3 <= int(i) <= 258).decode("utf-8", errors="replace")
+
     def encode_plus(self, text: str, max_length: int, padding: str = "max_length", truncation: bool = True,
                     padding_side: str = "right", **_) -> Dict[str, List[int]]:
         ids = self.encode(text)

@@ -1,0 +1,350 @@
+"""KV-cache generation: prefill, single-token decode steps and sampling from a :class:`Transformer`.
+
+Nothing here touches the training paths. ``prefill`` runs the ops of the training forward (embedding,
+fused add + norm, fused QKV GEMM, RoPE, the causal ``attn_fwd``, W1|W3 + SwiGLU, W2) with identical
+rounding points, keeps every layer's rotated k and plain v in a :class:`KVCache` and applies the final
+norm and the output GEMM to the last prompt row of each sequence only. ``decode_step`` pushes one token
+per sequence through all layers on the two kernels of csrc/kernels/attention_decode.hip:
+``rope_append`` (rotate q in place, write rotated k / plain v into the cache row ``kv_len[b]``) and
+``attn_decode`` (one query per sequence over the cache). ``kv_len`` lives on the device and no kernel
+argument depends on a host copy of it: a decode step never synchronises.
+
+The HIP decode kernels take bf16 / fp16 at head_dim 64 / 128. CPU tensors, fp32 / fp64 models on the
+GPU and other head dims run the torch math of :mod:`pyrecover_amd.ops.reference`
+(``attention_decode_ref`` / ``rope_append_ref``), noted once through ``_note_fallback`` like attention.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _ext
+from .config import TransformerModelArgs
+from .ops import fused as F
+from .ops import reference as ref
+
+SYNC_EVERY = 16  # generate(): the finished mask is read back at most once per this many tokens
+
+
+class KVCache:
+    """Per-layer k / v of shape [B, capacity, Hkv, D] (token-major, like every activation here) and the
+    int32 device tensor ``kv_len`` [B] of tokens held per sequence."""
+
+    def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device):
+        if capacity > model_args.seq_len:
+            raise ValueError(f"KVCache capacity {capacity} exceeds the model's seq_len {model_args.seq_len} "
+                             f"(the extent of the RoPE table)")
+        if batch < 1 or capacity < 1:
+            raise ValueError(f"KVCache needs batch >= 1 and capacity >= 1, got {batch}, {capacity}")
+        self.batch, self.capacity = batch, capacity
+        shape = (model_args.n_layers, batch, capacity, model_args.kv_heads, model_args.head_dim)
+        self._k = torch.zeros(shape, dtype=dtype, device=device)
+        self._v = torch.zeros(shape, dtype=dtype, device=device)
+        self.k = list(self._k.unbind(0))
+        self.v = list(self._v.unbind(0))
+        self.kv_len = torch.zeros(batch, dtype=torch.int32, device=device)
+
+    def nbytes(self) -> int:
+        return 2 * self._k.numel() * self._k.element_size()
+
+
+def _decode_hip(qkv: torch.Tensor, head_dim: int) -> bool:
+    return F._note_fallback("decode attention", qkv, _ext.hip16(qkv) and head_dim in (64, 128))
+
+
+def rope_append(qkv, tab, kv_len, k_cache, v_cache) -> None:
+    """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D]: q rotated in place, rotated k and plain v into
+    cache row clamp(kv_len[b], 0, cap - 1). Bit-equal to ``rope_`` on the same row at that position."""
+    if _decode_hip(qkv, k_cache.shape[-1]):
+        _ext.require_for(qkv).rope_append_(qkv, tab, kv_len, k_cache, v_cache)
+    else:
+        ref.rope_append_ref(qkv, tab, kv_len, k_cache, v_cache)
+
+
+def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """q [B, Hq, D] over the caches [B, cap, Hkv, D]: sequence b attends to keys 0 .. kv_len[b] - 1.
+    Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path)."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if _decode_hip(q, q.shape[-1]):
+        o, lse = _ext.require_for(q).attn_decode(q, k_cache, v_cache, kv_len, scale)
+        return o, lse
+    o, lse = ref.attention_decode_ref(q, k_cache, v_cache, kv_len, scale)
+    return o.to(q.dtype), lse
+
+
+# ---------------------------------------------------------------------------------------
+def _qkv_params(at):
+    return [at.wq.weight, at.wk.weight, at.wv.weight]
+
+
+def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc):
+    """The forward of ops/fused.py ``_AttentionBlock`` (same kernels, same rounding points), which also
+    leaves the rotated k and the plain v of positions 0 .. S - 1 in the cache."""
+    a = model.model_args
+    Hq, Hkv, D = a.n_heads, a.kv_heads, a.head_dim
+    at = layer.attention
+    w_qkv, w_o = model._weight(_qkv_params(at)), model._weight([at.wo.weight])
+    tab = model.rope_tab
+    T = B * S
+    x2 = n1.reshape(T, n1.shape[-1])
+    nq, nk = Hq * D, Hkv * D
+    if F._nt_ok(x2, w_qkv, "qkv") and D % 8 == 0 and tab.is_contiguous():
+        qkv = torch.empty(T, w_qkv.size(0), dtype=x2.dtype, device=x2.device)
+        _ext.require_for(x2).gemm_nt_(x2, w_qkv, qkv, 3, None, tab, S, D, nq + nk)
+    else:
+        qkv = torch.mm(x2, w_qkv.t())
+        if _ext.hip(qkv) and D % 8 == 0:
+            _ext.require_for(qkv).rope_(qkv, nq + nk, tab, D, S, 0, False, None)
+        else:
+            ref.rope_inplace_2d(qkv, nq + nk, tab, D, S)
+    q = qkv[:, :nq].view(B, S, Hq, D)
+    k = qkv[:, nq:nq + nk].view(B, S, Hkv, D)
+    v = qkv[:, nq + nk:].view(B, S, Hkv, D)
+    kc[:, :S].copy_(k)  # strided copies of the k / v views of the fused QKV activation
+    vc[:, :S].copy_(v)
+    o, _ = F._attn_fwd(q, k, v, 1.0 / math.sqrt(D), True)
+    return F._mm_nt(o.view(T, nq), w_o, "o").view(B, S, -1)
+
+
+def _mlp(model, layer, n2):
+    ff = layer.feed_forward
+    up = [ff.w1.weight, ff.w3.weight]
+    return F.swiglu_mlp(n2, model._weight(up), model._weight([ff.w2.weight]), model._slot(up),
+                        model._slot([ff.w2.weight]), up + [ff.w2.weight])
+
+
+def _head(model, h, pending):
+    """Final norm (with the last block's pending residual add) and the output GEMM on rows [B, dim]."""
+    if pending is None:
+        nf = model._norm(model.norm, h, None)
+    else:
+        _, nf = model._norm(model.norm, h, pending)
+    return torch.nn.functional.linear(nf, model.output.weight)
+
+
+def _check_cache(model, cache: KVCache, B: int):
+    a = model.model_args
+    if cache.batch != B or len(cache.k) != a.n_layers or tuple(cache.k[0].shape[2:]) != (a.kv_heads, a.head_dim):
+        raise ValueError("KVCache does not match the model / batch")
+    w = model.tok_embeddings.weight
+    if cache.k[0].dtype != w.dtype or cache.k[0].device != w.device:
+        raise ValueError(f"KVCache is {cache.k[0].dtype} on {cache.k[0].device}, the model {w.dtype} on {w.device}")
+
+
+@torch.no_grad()
+def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    """tokens [B, S] (ragged prompts right-padded), lens [B] in 1 .. S -> logits [B, V] of row
+    lens[b] - 1 of each sequence. Fills the cache rows 0 .. S - 1 and sets kv_len = lens. Causal
+    attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist."""
+    B, S = tokens.shape
+    _check_cache(model, cache, B)
+    if S > cache.capacity:
+        raise ValueError(f"prompt length {S} exceeds the cache capacity {cache.capacity}")
+    lens = lens.to(device=tokens.device, dtype=torch.long)
+    emb = model.tok_embeddings.weight
+    h = F.embedding(tokens, emb, model._slot([emb]))
+    pending = None
+    for i, layer in enumerate(model.layers.values()):
+        if pending is None:
+            x, n1 = h, model._norm(layer.attention_norm, h, None)
+        else:
+            x, n1 = model._norm(layer.attention_norm, h, pending)
+        att = _prefill_attention(model, layer, n1, B, S, cache.k[i], cache.v[i])
+        h, n2 = model._norm(layer.ffn_norm, x, att)
+        pending = _mlp(model, layer, n2)
+    cache.kv_len.copy_(lens.clamp(0, cache.capacity))
+    rows = (lens - 1).clamp(0, S - 1)
+    bi = torch.arange(B, device=tokens.device)
+    return _head(model, h[bi, rows].contiguous(), None if pending is None else pending[bi, rows].contiguous())
+
+
+@torch.no_grad()
+def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+    """One token per sequence (tokens [B], the token at position kv_len[b]) -> logits [B, V] for the
+    next position; kv_len grows by one (clamped at the capacity). No host synchronisation."""
+    B = tokens.shape[0]
+    _check_cache(model, cache, B)
+    a = model.model_args
+    Hq, Hkv, D = a.n_heads, a.kv_heads, a.head_dim
+    nq = Hq * D
+    scale = 1.0 / math.sqrt(D)
+    # once per step, not per layer: the lengths the attention sees, the new token included
+    att_len = (cache.kv_len + 1).clamp_(max=cache.capacity)
+    emb = model.tok_embeddings.weight
+    h = F.embedding(tokens.reshape(B, 1), emb, model._slot([emb])).view(B, -1)
+    pending = None
+    for i, layer in enumerate(model.layers.values()):
+        if pending is None:
+            x, n1 = h, model._norm(layer.attention_norm, h, None)
+        else:
+            x, n1 = model._norm(layer.attention_norm, h, pending)
+        at = layer.attention
+        qkv = torch.mm(n1, model._weight(_qkv_params(at)).t())
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i])
+        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale)
+        att = F._mm_nt(o.view(B, nq), model._weight([at.wo.weight]), "o")
+        h, n2 = model._norm(layer.ffn_norm, x, att)
+        pending = _mlp(model, layer, n2)
+    cache.kv_len.copy_(att_len)
+    return _head(model, h, pending)
+
+
+# ---------------------------------------------------------------------------------------
+def greedy_token(logits: torch.Tensor) -> torch.Tensor:
+    """argmax over the last dim; ties go to the lowest token id."""
+    V = logits.shape[-1]
+    top = logits.max(dim=-1, keepdim=True).values
+    ids = torch.arange(V, device=logits.device).expand_as(logits)
+    return torch.where(logits == top, ids, V).min(dim=-1).values.clamp_(max=V - 1)
+
+
+def filter_logits(logits: torch.Tensor, temperature: float, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+    """fp32 logits / temperature with everything outside the top-k set and the top-p nucleus at -inf. The
+    nucleus is the shortest prefix of the tokens sorted by probability whose mass reaches top_p."""
+    x = logits.float() / temperature
+    V = x.shape[-1]
+    if 0 < top_k < V:
+        kth = torch.topk(x, top_k, dim=-1).values[..., -1:]
+        x = x.masked_fill(x < kth, float("-inf"))
+    if top_p < 1.0:
+        sx, si = torch.sort(x, dim=-1, descending=True, stable=True)
+        p = torch.softmax(sx, dim=-1)
+        before = torch.cumsum(p, dim=-1) - p  # mass of the tokens ranked above
+        drop = before >= top_p
+        drop[..., 0] = False  # the most likely token always stays
+        x = x.masked_fill(torch.zeros_like(drop).scatter(-1, si, drop), float("-inf"))
+    return x
+
+
+def sample_token(logits: torch.Tensor, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """Next token ids [B] from logits [B, V]: greedy at temperature 0, else a draw from the filtered
+    softmax of the fp32 logits with ``generator``."""
+    if temperature == 0.0:
+        return greedy_token(logits)
+    probs = torch.softmax(filter_logits(logits, temperature, top_k, top_p), dim=-1)
+    return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
+
+
+def _model_device_dtype(model):
+    w = model.tok_embeddings.weight
+    return w.device, w.dtype
+
+
+@torch.no_grad()
+def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
+             top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
+             stats: Optional[Dict] = None) -> Tuple[List[List[int]], List[str]]:
+    """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
+
+    Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
+    ``max_new_tokens``, or ``length`` when the sequence filled the cache (the model's ``seq_len``).
+    ``temperature == 0`` is greedy (ties to the lowest id); otherwise fp32 logits are sampled with a
+    ``torch.Generator`` on the model's device seeded by ``seed``: same seed, same device, same tokens.
+    The finished mask lives on the device and is read back at most once per 16 generated tokens.
+    ``use_cache=False`` is the naive path (a full ``model(tokens)`` per new token): a debugging aid and
+    a second opinion. ``stats`` (a dict, optional) receives ``prefill_ms`` and ``decode_ms_per_token``
+    from device events on a GPU model (wall clock on the CPU)."""
+    if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
+        raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
+    device, dtype = _model_device_dtype(model)
+    args = model.model_args
+    B = len(prompts)
+    lens_host = [len(p) for p in prompts]
+    if B == 0 or min(lens_host) < 1:
+        raise ValueError("generate: every prompt needs at least one token")
+    S = max(lens_host)
+    if S > args.seq_len:
+        raise ValueError(f"generate: prompt length {S} exceeds the model's seq_len {args.seq_len}")
+    cap = min(args.seq_len, S + max_new_tokens)
+    buf = torch.zeros(B, cap, dtype=torch.long)
+    for b, p in enumerate(prompts):
+        buf[b, :len(p)] = torch.as_tensor(list(p), dtype=torch.long)
+    buf = buf.to(device)
+    lens = torch.tensor(lens_host, dtype=torch.long, device=device)
+    room = cap - lens  # [B]: tokens a sequence can still append
+    gen = None
+    if temperature > 0:
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+
+    timer = _Timer(device)
+    timer.mark()
+    if use_cache:
+        cache = KVCache(args, B, cap, dtype, device)
+        logits = prefill(model, buf[:, :S], lens, cache)
+    else:
+        bi = torch.arange(B, device=device)
+        logits = model(buf[:, :S])[bi, lens - 1]
+    timer.mark()
+
+    out = torch.full((B, max_new_tokens), -1, dtype=torch.long, device=device)
+    count = torch.zeros(B, dtype=torch.long, device=device)
+    done = torch.zeros(B, dtype=torch.bool, device=device)
+    steps = 0
+    for i in range(max_new_tokens):
+        tok = sample_token(logits, temperature, top_k, top_p, gen)
+        out[:, i] = torch.where(done, out[:, i], tok)
+        count += (~done).long()
+        if eos_id is not None:
+            done = done | (tok == eos_id)
+        done = done | (room <= i)  # token i was the last this sequence has a cache row for
+        if i + 1 == max_new_tokens:
+            break
+        if (i + 1) % SYNC_EVERY == 0 and bool(done.all().item()):
+            break
+        tok = torch.where(done, torch.zeros_like(tok), tok)
+        if use_cache:
+            logits = decode_step(model, tok, cache)
+        else:
+            col = (lens + i).clamp(max=cap - 1)
+            keep = buf.gather(1, col[:, None])[:, 0]
+            buf.scatter_(1, col[:, None], torch.where(done, keep, tok)[:, None])
+            L = min(S + i + 1, cap)
+            logits = model(buf[:, :L])[bi, (lens + i + 1).clamp(max=L) - 1]
+        steps += 1
+    timer.mark()
+    if stats is not None:
+        t = timer.intervals_ms()
+        stats["prefill_ms"] = t[0]
+        stats["decode_ms_per_token"] = t[1] / steps if steps else 0.0
+        stats["decode_steps"] = steps
+
+    out_h, count_h = out.cpu(), count.cpu().tolist()
+    tokens, reasons = [], []
+    for b in range(B):
+        ids = out_h[b, :count_h[b]].tolist()
+        tokens.append(ids)
+        if eos_id is not None and ids and ids[-1] == eos_id:
+            reasons.append("eos")
+        elif len(ids) == max_new_tokens:
+            reasons.append("max_new_tokens")
+        else:
+            reasons.append("length")
+    return tokens, reasons
+
+
+class _Timer:
+    """Marks on the current stream (device events on a GPU, the wall clock on the CPU)."""
+
+    def __init__(self, device):
+        self.cuda = device.type == "cuda"
+        self.marks = []
+
+    def mark(self):
+        if self.cuda:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.marks.append(e)
+        else:
+            import time
+
+            self.marks.append(time.perf_counter())
+
+    def intervals_ms(self) -> List[float]:
+        if self.cuda:
+            self.marks[-1].synchronize()
+            return [a.elapsed_time(b) for a, b in zip(self.marks, self.marks[1:])]
+        return [(b - a) * 1e3 for a, b in zip(self.marks, self.marks[1:])]

@@ -203,3 +203,47 @@ def cross_entropy_reg_ref(logits, labels, ignore_index: int = -100, z_loss: floa
         stats = torch.stack([obj, nf, ce, zt, sv, lv.sum() / nf, lv.abs().max() if lv.numel() else zero.sum(),
                              torch.zeros_like(nf)]).detach()
     return obj, stats
+
+
+# ---------------------------------------------------------------------------------------
+# KV-cache generation (pyrecover_amd/inference.py; HIP: csrc/kernels/attention_decode.hip)
+def attention_decode_ref(q, k_cache, v_cache, kv_len, scale: Optional[float] = None):
+    """One query per sequence over a KV cache, in the input's precision promoted to at least fp32.
+
+    q [B, Hq, D]; k_cache, v_cache [B, cap, Hkv, D]; kv_len integer [B] (clamped into [0, cap]):
+    sequence b attends to keys 0 .. kv_len[b] - 1, and whatever the caches hold beyond that (NaN and
+    Inf included) never reaches the output. Returns (o [B, Hq, D] in that precision, lse [B, Hq]);
+    length 0 gives o = 0 and lse = -inf."""
+    B, Hq, D = q.shape
+    cap, Hkv = k_cache.shape[1], k_cache.shape[2]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    n = kv_len.to(device=q.device, dtype=torch.long).clamp(0, cap)
+    dead = torch.arange(cap, device=q.device).view(1, cap) >= n.view(B, 1)  # [B, cap]
+    qg = up(q).view(B, Hkv, Hq // Hkv, D)
+    kk, vv = up(k_cache), up(v_cache).masked_fill(dead.view(B, cap, 1, 1), 0)
+    s = torch.einsum("bhgd,bkhd->bhgk", qg, kk) * scale
+    s = s.masked_fill(dead.view(B, 1, 1, cap), float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.clamp_min(torch.finfo(s.dtype).min).unsqueeze(-1))  # an empty row: exp(-inf) = 0
+    o = torch.einsum("bhgk,bkhd->bhgd", p, vv)
+    return o.reshape(B, Hq, D), lse.reshape(B, Hq)
+
+
+def rope_append_ref(qkv, tab, kv_len, k_cache, v_cache) -> None:
+    """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D] at positions pos[b] = clamp(kv_len[b], 0, cap - 1):
+    q is rotated in place, the rotated k and the plain v are written into row pos[b] of the caches
+    (RoPE math of :func:`rope_inplace_2d`: opmath rotation from table row pos[b], one rounding)."""
+    B = qkv.shape[0]
+    cap, Hkv, D = k_cache.shape[1:]
+    nk = Hkv * D
+    nq = qkv.shape[1] - 2 * nk
+    pos = kv_len.to(device=qkv.device, dtype=torch.long).clamp(0, cap - 1)
+    rows = tab[pos].to(up(qkv).dtype)  # [B, D/2, 2]
+    c, s = rows[..., 0].unsqueeze(1), rows[..., 1].unsqueeze(1)
+    x = up(qkv[:, :nq + nk]).reshape(B, (nq + nk) // D, D // 2, 2)
+    a, b = x[..., 0], x[..., 1]
+    rot = torch.stack([a * c - b * s, a * s + b * c], dim=-1).reshape(B, nq + nk).to(qkv.dtype)
+    qkv[:, :nq] = rot[:, :nq]
+    bi = torch.arange(B, device=qkv.device)
+    k_cache[bi, pos] = rot[:, nq:].view(B, Hkv, D)
+    v_cache[bi, pos] = qkv[:, nq + nk:].view(B, Hkv, D)

@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Decode-attention benchmark: ``attn_decode`` alone and a whole ``decode_step`` (tool, not a test).
+
+Two shapes: the 7B shape (B 16, context 2048, MHA 32/32, head_dim 128) and the Llama-3-8B shape (B 1,
+context 8192, GQA 32/8, head_dim 128). Prints microseconds and the achieved bytes/s of K/V read, next to
+the same call through ``attention_decode_ref`` (torch math) on the GPU. The kernel streams K and V once,
+so it is read against the achievable HBM streaming rate of MI355X (6.0-6.3 TB/s).
+
+Every timed call reads another layer's cache (as a decode step does), and the layers together exceed the
+256 MiB Infinity Cache, so the rate is an HBM rate and not a cache-hit rate.
+
+    python tools/decode_bench.py [--layers 4] [--iters 50] [--skip-step] [--shapes 7b,llama3-8b]
+
+The times are device events around back-to-back calls: at batch 1 a call (two small kernels plus the
+binding's allocations) can cost the host more than the kernels take, so read the kernels' own time from a
+`rocprofv3 --kernel-trace --stats -- python tools/decode_bench.py --skip-step --shapes llama3-8b` run.
+"""
+import argparse
+import math
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from pyrecover_amd import _ext  # noqa: E402
+from pyrecover_amd import inference as inf  # noqa: E402
+from pyrecover_amd.config import get_preset  # noqa: E402
+from pyrecover_amd.models.llama import Transformer  # noqa: E402
+from pyrecover_amd.ops import reference as ref  # noqa: E402
+
+SHAPES = [("7b", "llama2-7b", 16, 2048), ("llama3-8b", "llama3-8b", 1, 8192)]
+L3_BYTES = 256 << 20
+
+
+def timed_us(fn, iters, warmup=5):
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(iters):
+        fn(i)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def bench_attention(name, cfg, B, ctx, iters, dev):
+    C = _ext.native()
+    Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
+    per_layer = 2 * B * ctx * Hkv * D * 2  # bytes of K and V one call reads
+    n_buf = max(2, -(-2 * L3_BYTES // per_layer))  # rotate over >= 2 x the Infinity Cache
+    ks = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    vs = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    q = torch.randn(B, Hq, D, device=dev).bfloat16()
+    n = torch.full((B,), ctx, device=dev, dtype=torch.int32)
+    scale = 1 / math.sqrt(D)
+    hip = timed_us(lambda i: C.attn_decode(q, ks[i % n_buf], vs[i % n_buf], n, scale), iters)
+    tor = timed_us(lambda i: ref.attention_decode_ref(q, ks[i % n_buf], vs[i % n_buf], n, scale), max(5, iters // 5), 2)
+    o, _ = C.attn_decode(q, ks[0], vs[0], n, scale)
+    o_ref, _ = ref.attention_decode_ref(q, ks[0], vs[0], n, scale)
+    err = (o.float() - o_ref).abs().max().item()
+    print(f"{name}: attn_decode B={B} ctx={ctx} Hq/Hkv={Hq}/{Hkv} D={D} KC={C.attn_decode_chunk()} "
+          f"({per_layer / 2**20:.0f} MiB of K/V per call, {n_buf} caches in rotation)")
+    print(f"  HIP   {hip:9.1f} us  {per_layer / hip / 1e6:6.2f} TB/s")
+    print(f"  torch {tor:9.1f} us  {per_layer / tor / 1e6:6.2f} TB/s   (HIP is {tor / hip:.1f}x; max |o - o_ref| {err:.2e})")
+    return hip, tor
+
+
+def bench_step(name, preset, B, ctx, layers, iters, dev):
+    cfg = get_preset(preset, n_layers=layers, seq_len=ctx)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    with torch.device(dev):
+        model = Transformer(cfg)
+    torch.set_default_dtype(prev)
+    model.eval()
+    model.flatten_(shadows=False)
+    cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev)
+    for k, v in zip(cache.k, cache.v):
+        k.normal_()
+        v.normal_()
+    tok = torch.randint(0, cfg.vocab_size, (B,), device=dev)
+
+    def step(_):
+        cache.kv_len.fill_(ctx - 1)  # the step appends row ctx - 1 and attends to all ctx keys
+        inf.decode_step(model, tok, cache)
+
+    us = timed_us(step, iters)
+    kv = cache.nbytes()
+    print(f"{name}: decode_step, {layers} layers, B={B} ctx={ctx}: {us:9.1f} us ({us / layers:.1f} us per layer; "
+          f"K/V read {kv / us / 1e6:.2f} TB/s of step time)")
+    return us
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=4, help="layers of the model the decode_step timing builds")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--shapes", default="7b,llama3-8b", help="comma list of: 7b, llama3-8b")
+    a = ap.parse_args()
+    shapes = [s for s in SHAPES if s[0] in a.shapes.split(",")]
+    dev = torch.device("cuda", 0)
+    _ext.native()
+    for name, preset, B, ctx in shapes:
+        bench_attention(name, get_preset(preset), B, ctx, a.iters, dev)
+    if not a.skip_step:
+        for name, preset, B, ctx in shapes:
+            bench_step(name, preset, B, ctx, a.layers, max(10, a.iters // 2), dev)
+
+
+if __name__ == "__main__":
+    main()
