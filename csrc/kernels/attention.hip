@@ -490,7 +490,7 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
 // stay resident in LDS (read as MFMA operands, so only the dK/dV accumulators live in registers
 // and the kernel fits 2 waves/SIMD); 32-row Q/dO tiles stream through a single LDS buffer,
 // register-staged one tile ahead. Loops over the query heads of the kv head (GQA) and query tiles.
-//   S  = Q K^T   (key on lane)      P  = exp2(S*c - lse*log2e)
+//   S  = Q K^T   (key on lane)      P  = exp2(S*c - lse*log2e), c = scale*log2e applied to the fp32 score
 //   dP = dO V^T  (key on lane)      dS = P * (dP - delta)
 //   dV^T += dO^T P                  dK^T += Q^T dS      (accumulators reused as B operands)
 // NW = 8 (256 keys, 144 KB LDS, one 512-thread block per CU): each staged Q/dO tile feeds twice
@@ -513,7 +513,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
   constexpr bool ROWC_LDS = NW == 8;
   // Q and dO first: their (transposed) reads then use 16-bit immediate offsets off one base
   __shared__ __attribute__((aligned(16))) T smem[2 * KVT + 2 * QDT];  // Q dO K V
-  __shared__ __attribute__((aligned(16))) float rowc[ROWC_LDS ? 2 : 1][32];  // lse*log2e | delta
+  __shared__ __attribute__((aligned(16))) float rowc[ROWC_LDS ? 2 : 1][32];  // NW = 8: -lse/scale | -delta
   T* const Qs = smem;
   T* const Ds = smem + QDT;
   T* const Ks = smem + 2 * QDT;
@@ -551,8 +551,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
   const int nqt = (S - qstart) / QT;
   const int total = nqt * nrep;
   // lane reads the row constant of query row l32 of the tile: lse*log2e (h2 = 0) or delta (h2 = 1);
-  // NW = 8 stages them negated: they are the S / dP accumulators' initial values (below)
-  const float rc_mul = ROWC_LDS ? (h2 ? -1.f : -1.4426950408889634f) : (h2 ? 1.f : 1.4426950408889634f);
+  // NW = 8 stages -lse / scale and -delta: they are the S / dP accumulators' initial values (below);
+  // -lse / scale is a division, as in the dQ kernel's RC2 (the ring kernel's input: bitwise equal gradients)
+  const float rc_mul = h2 ? 1.f : 1.4426950408889634f;  // NW = 4
   const float* rc_base = (h2 ? Delta : LSE) + (long)b * Hq * S + l32;
   int bp_base = 4 * (4 * h2);  // ds_bpermute byte address of lane crow(0, h2)
   asm volatile("" : "+v"(bp_base));  // opaque: per-row offsets then fold into the ds offset field
@@ -564,29 +565,24 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
     const int q0 = qstart + (it % nqt) * QT;
     sq.load(Q + (long)b * S * ldq + hq * D, ldq, q0, S);
     sd.load(dO + (long)b * S * lddo + hq * D, lddo, q0, S);
-    if (ROWC_LDS && wid == 0) rc_next = rc_base[(long)hq * S + q0] * rc_mul;
+    if (ROWC_LDS && wid == 0) {
+      const float x = rc_base[(long)hq * S + q0];
+      rc_next = h2 ? -x : -x / scale;
+    }
   };
   if (total > 0) stage_load(0);
   if constexpr (ROWC_LDS) {
-    // K pre-multiplied by c = scale * log2(e) in LDS, once per block (one extra rounding of K to T):
-    // each wave rescales its own 32 contiguous rows (8 KiB of the image), which only it reads
+    // K of the block has landed (KREG reads it below). K stays as stored: c = scale * log2(e) multiplies
+    // the fp32 score, because a K c rounded to T moves every score by u |q||k| scale, which exp turns into
+    // a relative error of P that grows with the size of the scores
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    char* kb = reinterpret_cast<char*>(Ks) + kg * 32 * D * (int)sizeof(T);
-#pragma unroll
-    for (int i = 0; i < 32 * D * (int)sizeof(T) / 1024; ++i) {
-      V8<T>& c8 = *reinterpret_cast<V8<T>*>(kb + i * 1024 + lane * 16);
-      V8<T> v8 = c8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v8[j] = (T)((float)v8[j] * scale_log2);
-      c8 = v8;
-    }
   }
-  static_assert(!KREG || ROWC_LDS, "KREG reads the prescaled K image of the NW = 8 kernel");
+  static_assert(!KREG || ROWC_LDS, "KREG is an instantiation of the NW = 8 kernel");
   V8<T> kf[KREG ? NKS : 1];
   if constexpr (KREG) {
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) kf[ks] = lo.rowk(Kw, 0, ks);  // the wave's own rows (rescaled above)
+    for (int ks = 0; ks < NKS; ++ks) kf[ks] = lo.rowk(Kw, 0, ks);  // the wave's own rows
   }
 
   for (int it = 0; it < total; ++it) {
@@ -606,9 +602,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
       const bool diag = CAUSAL && q0 == kw;
       f32x16 s = f32x16{}, dp = f32x16{};
       if constexpr (ROWC_LDS) {
-        // S' = (c K) Q^T - lse log2(e), dP' = dO V^T - delta: the accumulators start at the
+        // S' = K Q^T - lse / scale, dP' = dO V^T - delta: the accumulators start at the
         // (negated) row constants of their query rows crow(r, h2); on the diagonal tile the causal
-        // mask rides on the S initial values (-inf)
+        // mask rides on the S initial values (-inf); P = exp2(c S')
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const float4 a = *reinterpret_cast<const float4*>(&rowc[0][8 * rr + 4 * h2]);
@@ -643,7 +639,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
       if constexpr (ROWC_LDS) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          float p = fexp2(s[r]);
+          float p = fexp2(s[r] * scale_log2);
           if (!CAUSAL && krow >= skv) p = 0.f;  // padded key
           s[r] = p;
           dp[r] = p * dp[r];
@@ -695,10 +691,10 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dkdv_kernel(
 
 // ======================================================================================
 // Backward dK/dV, ring-staged (NW = 8, S % 256 == 0): the bwd_dkdv_kernel<.., 8, .., KREG> math with
-//  * K of the wave's 32 keys loaded straight from global memory into registers (pre-multiplied by
-//    scale log2(e) there), so K takes no LDS and its 8 row reads per query tile are gone;
+//  * K of the wave's 32 keys loaded straight from global memory into registers, so K takes no LDS and
+//    its 8 row reads per query tile are gone;
 //  * V of the block resident in LDS (LDS-DMA), read as the dP chain's row operand;
-//  * Q / dO tiles and their row constants (-lse log2(e), -delta: the dQ kernel's RC2 output) moved by
+//  * Q / dO tiles and their row constants (-lse / scale, -delta: the dQ kernel's RC2 output) moved by
 //    LDS-DMA into a double buffer one tile ahead: no VGPR staging, no ds_write, and ONE barrier per
 //    32-query tile instead of two.
 // LDS: 64 KB (V) + 2 x 16.25 KB at D = 128.
@@ -713,7 +709,7 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
   constexpr int NKS = D / 16, NDB = D / 32;
   constexpr int KVT = KB * D, QDT = QT * D;
   __shared__ __attribute__((aligned(16))) T Vs[KVT];
-  // per buffer: Q | dO tiles, then 64 floats: -lse log2(e) [32] | -delta [32] (one object per buffer:
+  // per buffer: Q | dO tiles, then 64 floats: -lse / scale [32] | -delta [32] (one object per buffer:
   // separate alias scopes, so reads of one buffer do not wait for the DMA filling the other)
   __shared__ __attribute__((aligned(16))) T qd0[2 * QDT];
   __shared__ __attribute__((aligned(16))) T qd1[2 * QDT];
@@ -744,16 +740,12 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
   LaneOff<T, D> lo;
   lo.init(lane);
 
-  // the wave's K rows as the S chain's B operand: lane holds K[krow][16 ks + 8 h2 .. + 7] * c
+  // the wave's K rows as the S chain's B operand: lane holds K[krow][16 ks + 8 h2 .. + 7]
   V8<T> kf[NKS];
   {
     const T* kr = K + ((long)b * S + krow) * ldk + hk * D + 8 * h2;
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      kf[ks] = *reinterpret_cast<const V8<T>*>(kr + 16 * ks);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kf[ks][j] = (T)((float)kf[ks][j] * scale_log2);
-    }
+    for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const V8<T>*>(kr + 16 * ks);
   }
 
   f32x16 dkt[NDB], dvt[NDB];
@@ -769,7 +761,7 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
     const int q0 = qstart + (it % nqt) * QT;
     gq.issue(Q + ((long)b * S + q0) * ldq + hq * D, qd);
     gd.issue(dO + ((long)b * S + q0) * lddo + hq * D, qd + QDT);
-    if (wid == 0 && lane < 16) {  // 2 x 128 B of row constants: lanes 0-7 -lse log2(e), 8-15 -delta
+    if (wid == 0 && lane < 16) {  // 2 x 128 B of row constants: lanes 0-7 -lse / scale, 8-15 -delta
       const float* src = RC + (lane < 8 ? 0 : nrc) + rc_b + (long)hq * S + q0 + 4 * (lane & 7);
       __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)rc, 16, 0, 0);
@@ -788,8 +780,8 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
     const int q0 = qstart + (it % nqt) * QT;
     if (!(CAUSAL && q0 + QT - 1 < kw)) {
       const bool diag = CAUSAL && q0 == kw;
-      // S' = (c K) Q^T - lse log2(e), dP' = dO V^T - delta: the accumulators start at the row
-      // constants of their query rows crow(r, h2); the causal mask rides on S's initial values
+      // S' = K Q^T - lse / scale, dP' = dO V^T - delta: the accumulators start at the row constants
+      // of their query rows crow(r, h2); the causal mask rides on S's initial values; P = exp2(c S')
       f32x16 sa, dp;
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
@@ -819,7 +811,7 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float p = fexp2(sa[r]);
+        float p = fexp2(sa[r] * scale_log2);
         if (!CAUSAL && krow >= skv) p = 0.f;  // padded key
         sa[r] = p;
         dp[r] = p * dp[r];
@@ -861,12 +853,14 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_r_kernel(
 //   [S,dP of A] -> [S,dP of B | softmax A] -> [dV,dK += A | softmax B] -> [dV,dK += B]
 // K/V of the block land in LDS (64 KB at D = 128) and each wave keeps its own rows' fragments in
 // registers from then on. Q/dO steps (32 KB) and their per-query constants arrive by LDS-DMA into a
-// double buffer, issued one step ahead. The constants are -lse log2(e) and -delta, written by the dQ
-// kernel (RC2), and they are the INITIAL values of the S and dP accumulators; with K pre-multiplied
-// by c = scale log2(e) and the causal mask folded into the S initial values on diagonal steps,
-// S' = (c K) Q^T - lse log2(e) and dP' = dO V^T - delta leave the MFMA chains ready: each score
-// costs exp2(S') and dS = P dP' (4 VALU fewer per element than exp2(fma(S, c, -lse log2e)), a mask
-// select and P (dP - delta), in this VALU-bound one-wave kernel).
+// double buffer, issued one step ahead. The constants are -lse / scale and -delta, written by the dQ
+// kernel (RC2), and they are the INITIAL values of the S and dP accumulators; with the causal mask
+// folded into the S initial values on diagonal steps, S' = K Q^T - lse / scale and
+// dP' = dO V^T - delta leave the MFMA chains ready: each score costs exp2(c S'), c = scale log2(e),
+// and dS = P dP' (3 VALU fewer per element than exp2(fma(S, c, -lse log2e)), a mask select and
+// P (dP - delta), in this VALU-bound one-wave kernel). K is NOT pre-multiplied by c: rounding K c to T
+// moves every score by u |q||k| scale, and exp turns that into a relative error of P that grows with
+// the scores (dV 12-25 u on scores of tens of nats; profiles/attn_rowerr/README.md).
 // ======================================================================================
 template <typename T, int D, bool CAUSAL>
 __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void bwd_dkdv_p2_kernel(
@@ -878,7 +872,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void bwd_dkdv_p2_kernel(
   constexpr int NW = 4, KB = 32 * NW, QS = 64;
   constexpr int NKS = D / 16, NDB = D / 32;
   constexpr int KVT = KB * D, QDT = QS * D;
-  // Q0 dO0 Q1 dO1 (steps, double-buffered) | K V | row constants [buf][-lse log2(e), -delta][64]
+  // Q0 dO0 Q1 dO1 (steps, double-buffered) | K V | row constants [buf][-lse / scale, -delta][64]
   __shared__ __attribute__((aligned(16))) T smem[4 * QDT + 2 * KVT];
   __shared__ __attribute__((aligned(16))) float rowc[2][2][QS];
   T* const Ks = smem + 4 * QDT;
@@ -907,7 +901,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void bwd_dkdv_p2_kernel(
     const int q0 = qstart + (t % nqs) * QS;
     gq.issue(Q + ((long)b * S + q0) * ldq + hq * D, smem + buf * 2 * QDT);
     gd.issue(dO + ((long)b * S + q0) * lddo + hq * D, smem + buf * 2 * QDT + QDT);
-    if (wid < 2) {  // wave 0: -lse log2(e), wave 1: -delta (one dword per lane)
+    if (wid < 2) {  // wave 0: -lse / scale, wave 1: -delta (one dword per lane)
       const float* src = (wid ? NDelta : NLS) + ((long)b * Hq + hq) * S + q0 + lane;
       __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)&rowc[buf][wid][0], 4, 0, 0);
@@ -933,14 +927,10 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void bwd_dkdv_p2_kernel(
   // the wave's K and V row fragments (B operands of S and dP, the same for every step) are read
   // from LDS once and kept in registers (B1 S8192 H32/8 dK/dV+dQ 1.871 -> 1.851 ms,
   // profiles/r3/attn_ab_kvreg.log)
-  // K is pre-multiplied by c = scale * log2(e) once (one extra rounding of K to T), so S = (c K) Q^T
-  // needs no per-score multiply before its exp2
   V8<T> kf[NKS], vf[NKS];
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     kf[ks] = lo.rowk(Kw, 0, ks);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) kf[ks][j] = (T)((float)kf[ks][j] * scale_log2);
     vf[ks] = lo.rowk(Vw, 0, ks);
   }
 
@@ -1002,7 +992,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void bwd_dkdv_p2_kernel(
         }
       };
       auto soft = [&](f32x16& sv, f32x16& dp, int u, int r) {
-        float p = fexp2(sv[r]);  // sv = (c K) Q^T - lse log2(e), -inf where masked
+        float p = fexp2(sv[r] * scale_log2);  // sv = K Q^T - lse / scale, -inf where masked
         if (!CAUSAL && kw + l32 >= skv) p = 0.f;  // padded key
         sv[r] = p;
         dp[r] = p * dp[r];  // dp = dP - delta
@@ -1162,8 +1152,8 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dq_kernel(
     if (qrow < S && h2 == 0) {
       const long i = ((long)b * Hq + hq) * S + qrow;
       Delta[i] = dl;
-      if (RC2 != nullptr) {  // row constants of the pipelined dK/dV kernel: -lse log2(e), -delta
-        RC2[i] = -lse2;
+      if (RC2 != nullptr) {  // row constants of the pipelined / ring dK/dV kernel: -lse / scale, -delta
+        RC2[i] = -LSE[i] / scale;
         RC2[nrc + i] = -dl;
       }
     }
@@ -1501,7 +1491,7 @@ static bool attn_bwd_use_fused(int B, int S, int Hq, int Hkv, int D, int skv) {
   return grid >= cus && grid * 10 >= rounds * cus * 9;
 }
 
-// fp32 workspace of pra_attn_bwd, in floats: delta, the row constants (-lse log2(e), -delta) of the
+// fp32 workspace of pra_attn_bwd, in floats: delta, the row constants (-lse / scale, -delta) of the
 // pipelined dK/dV kernel and the fused kernel, the dK/dV split partials, or the fused kernel's dQ partials
 long attn_bwd_ws_floats(int B, int S, int Hq, int Hkv, int D) {
   const long nrc = (long)B * Hq * S;
@@ -1533,7 +1523,7 @@ hipError_t attn_bwd_t(const void* q, const void* k, const void* v, const void* o
   // 8-wave (256-row) blocks; S % 256 != 0 (S % 128 == 0) takes the 4-wave instantiations
   const int nw = S % 256 ? 4 : 8;
   // delta: fp32 workspace [3][B * Hq * S]: delta, then the pipelined dK/dV kernel's row constants
-  // (-lse log2(e), -delta), written by the dQ kernel only when that kernel runs
+  // (-lse / scale, -delta), written by the dQ kernel only when that kernel runs
   const long nrc = (long)B * Hq * S;
   const bool p2 = dkdv_use_p2(B, S, Hq, Hkv, D);
   const bool ring = (g_attn_opts.dkdv_kreg == 2 || (g_attn_opts.dkdv_kreg == -2 && mid_event == nullptr)) && !p2 &&

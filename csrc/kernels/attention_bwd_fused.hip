@@ -8,15 +8,15 @@
 // workgroup owns a whole (batch, kv head) -- all its key blocks and every query head of its GQA group
 // -- and walks the key blocks in order, so the dQ sum has ONE writer and a fixed order:
 //
-//   for each 256-key block kb (K, V resident in LDS, K pre-multiplied by c = scale log2 e):
+//   for each 256-key block kb (K, V resident in LDS), c = scale log2 e:
 //     for each query head hq of the group, each 32-query tile q0 the block can see:
-//       8 waves x 32 keys: S' = Q (cK)^T - lse log2 e, dP' = dO V^T - delta   (row constants = the
-//         accumulators' initial values), P = exp2(S'), dS = P dP'; dV^T += dO^T P, dK^T += Q^T dS
+//       8 waves x 32 keys: S' = Q K^T - lse / scale, dP' = dO V^T - delta   (row constants = the
+//         accumulators' initial values), P = exp2(c S'), dS = P dP'; dV^T += dO^T P, dK^T += Q^T dS
 //         (accumulators in registers for the whole block); dS -> LDS (key-major image)
 //       barrier
-//       waves 0-3, 32 head dims each: dQ^T = (cK)^T dS^T over the block's 256 keys (16 MFMAs), added
+//       waves 0-3, 32 head dims each: dQ^T = K^T dS^T over the block's 256 keys (16 MFMAs), added
 //         to the tile's fp32 partial of the previous blocks (kept in a workspace, read back by the
-//         same lane that wrote it); the last block that sees the tile writes dQ = ln2 * sum (with
+//         same lane that wrote it); the last block that sees the tile writes dQ = scale * sum (with
 //         the inverse RoPE) instead.
 //     dK, dV of the block -> global (with dK's inverse RoPE)
 //
@@ -34,14 +34,14 @@
 namespace pra {
 namespace attn {
 
-// RC[i] = -lse[i] log2(e), RC[nrc + i] = -delta[i], delta = rowsum(dO * O); i = (b Hq + hq) S + q.
+// RC[i] = -lse[i] / scale, RC[nrc + i] = -delta[i], delta = rowsum(dO * O); i = (b Hq + hq) S + q.
 // 16 lanes per row (8 elements each at D = 128), rows in TOKEN order (t Hq + hq), so a wave reads
 // 4 consecutive 256-B head rows of one token: in (b, hq, q) order consecutive rows were a token
 // stride (8 KiB at 7B) apart and the pass took 0.47 ms instead of ~0.1 at B16 S2048 H32.
 template <typename T>
 __global__ __launch_bounds__(256) void bwd_rowc_kernel(const T* __restrict__ O, const T* __restrict__ dO,
                                                        const float* __restrict__ LSE, float* __restrict__ RC,
-                                                       long nrc, int S, int Hq, long ldo, long lddo) {
+                                                       long nrc, int S, int Hq, long ldo, long lddo, float scale) {
   constexpr int D = 128;
   const long row = ((long)blockIdx.x * 256 + threadIdx.x) >> 4;  // token-major: tok Hq + hq
   const int sub = threadIdx.x & 15;
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void bwd_rowc_kernel(const T* __restrict__ O, 
   if (sub == 0 && row < nrc) {
     const long b = tok / S, q = tok % S;
     const long i = (b * Hq + hq) * S + q;
-    RC[i] = -LSE[i] * 1.4426950408889634f;
+    RC[i] = -LSE[i] / scale;
     RC[nrc + i] = -part;
   }
 }
@@ -117,7 +117,6 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
   char* const srow = reinterpret_cast<char*>(Ss) + 512 * (srw >> 3) + 64 * (srw & 7) + 8 * h2;
   const int ssw = (l32 >> 2) & 3;
   auto sput = [&](int g, uint2 v) { *reinterpret_cast<uint2*>(srow + 16 * (g ^ ssw)) = v; };
-  const float ln2 = 0.69314718055994531f;
   // this workgroup's scratch line (4 KiB after the dQ partials): the stand-in address of the
   // loads / stores a wave issues only to keep the memory-operation count uniform
   float* const scratch = dQacc + nrc * D + (long)blockIdx.x * 1024 + 4 * lane;
@@ -137,18 +136,8 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
     stage(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    {  // K *= c in place: each wave rescales its own 32 rows (8 KiB of the image); the others read
-       // them only after the first tile's barrier
-      char* kp = reinterpret_cast<char*>(Ks) + wid * 32 * D * (int)sizeof(T);
-#pragma unroll
-      for (int i = 0; i < 32 * D * (int)sizeof(T) / 1024; ++i) {
-        V8<T>& c8 = *reinterpret_cast<V8<T>*>(kp + i * 1024 + lane * 16);
-        V8<T> v8 = c8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v8[j] = (T)((float)v8[j] * scale_log2);
-        c8 = v8;
-      }
-    }
+    // K stays as stored: c = scale log2(e) multiplies the fp32 score (P = exp2(c S')), see
+    // bwd_dkdv_p2_kernel in attention.hip
     f32x16 dkt[NDB], dvt[NDB];
 #pragma unroll
     for (int i = 0; i < NDB; ++i) {
@@ -195,7 +184,7 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
 #endif
       sq.store(Qs);
       sd.store(Ds);
-      __syncthreads();  // Q / dO of this tile (and, at it = 0, the block's scaled K) visible
+      __syncthreads();  // Q / dO of this tile visible
       stage(it + 1 < total ? it + 1 : it);  // (the last tile re-loads itself: same load count every tile)
       if (!(CAUSAL && q0 + QT - 1 < kw)) {
         if (CAUSAL && q0 == kw) {  // diagonal tile: keys after the query are masked on S's initial values
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = fexp2(sa[r]);
+          const float p = fexp2(sa[r] * scale_log2);
           sa[r] = p;
           dp[r] = p * dp[r];
         }
@@ -283,7 +272,7 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
 #endif
       if (wid < 4 && last) {
         const f32x16 fin[1] = {acc};
-        store_rows16<T, 1>(fin, ln2, dQ + ((long)b * S + q0 + l32) * lddq + hq * D + 32 * wid, true, h2,
+        store_rows16<T, 1>(fin, scale, dQ + ((long)b * S + q0 + l32) * lddq + hq * D + 32 * wid, true, h2,
                            rtab ? rtab + (long)(q0 + l32) * (D / 2) + 16 * wid : nullptr);
         if (!rtab) {  // two more (scratch) stores: at least four memory operations on every path
           *reinterpret_cast<float4*>(scratch) = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -328,7 +317,7 @@ hipError_t pra_attn_bwd_fused(int dtype, const void* q, const void* k, const voi
   const dim3 g0((unsigned)((nrc * 16 + 255) / 256)), g1((unsigned)(B * Hkv));
 #define PRA_FUSED(TT)                                                                                          \
   hipLaunchKernelGGL((bwd_rowc_kernel<TT>), g0, dim3(256), 0, st, (const TT*)o, (const TT*)dout, lse, rc, nrc, S, \
-                     Hq, ldo, lddo);                                                                           \
+                     Hq, ldo, lddo, scale);                                                                    \
   if (mid_event != nullptr && hipEventRecord(mid_event, st) != hipSuccess) return hipErrorInvalidResourceHandle; \
   if (causal)                                                                                                  \
     hipLaunchKernelGGL((bwd_fused_kernel<TT, true>), g1, dim3(512), 0, st, (const TT*)q, (const TT*)k,         \

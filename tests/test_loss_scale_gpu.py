@@ -340,24 +340,43 @@ def test_fp16_master_with_dynamic_scale_tracks_fp32_torch_reference(cuda, torch_
     assert gap < 0.1 * theirs[0], (gap, curves)
 
 
+def _tracked(ours, theirs, bound):
+    """Number of leading steps whose loss stays within `bound` of the reference; a NaN loss is outside."""
+    n = 0
+    for o, t in zip(ours, theirs):
+        if not abs(o - t) < bound:
+            break
+        n += 1
+    return n
+
+
 def test_pure_fp16_with_dynamic_scale_is_no_worse_than_unscaled(cuda, torch_curve):
     """Pure fp16 (fp16 parameters AND fp16 moments) does not fit the existing tolerance (0.1 x the initial
     loss = 0.572) with or without a loss scale: the second moment (1 - b2) g^2 of a typical gradient
     element (|g| ~ 1e-3) is below fp16's smallest number whatever the loss scale, because the moments
-    hold the unscaled gradient, so those elements step by lr * m / eps. Measured on an MI355X at
-    this learning rate: the unscaled run (the parent commit's only fp16 mode) reaches a NaN loss
-    within the first six steps and stays there -- its gap is not a number, counted as infinite; the
-    run under --loss-scale dynamic skips the non-finite steps (11 of 60), keeps loss and parameters
-    finite, and its gap is 809.7. The scaled run is required to be no worse than the unscaled one,
-    and to stay finite, which the unscaled one does not. (fp16 that trains needs --master-weights
-    fp32: the test above.)"""
+    hold the unscaled gradient, so those elements step by lr * m / eps. Both runs therefore leave the
+    reference within the first steps and end with losses in the thousands (measured on an MI355X: both
+    follow it for 2 steps; largest distance 4359 unscaled, 4539 under --loss-scale dynamic, which skips
+    13 of 60 steps and keeps loss and parameters finite). Until the dK/dV kernels stopped rounding K * scale * log2(e) to fp16, the diverged
+    parameters overflowed that product and the unscaled run sat at a NaN loss from the sixth step on, which
+    made `gap <= gap_plain` trivially true; between two diverged runs it is a coin toss. The scaled run is
+    required to stay finite, to follow the reference for at least as many leading steps (within the
+    existing tolerance) as the unscaled one, and to have no larger a gap whenever the unscaled run still
+    learns anything (its gap below the loss of the untrained model; a NaN loss is infinitely far and never
+    counts as learning). (fp16 that trains needs --master-weights fp32: the test above.)"""
     init, theirs = torch_curve
     plain, _, _ = _track_fp16(cuda, init, scaled=False, master=False)
     ours, st, params = _track_fp16(cuda, init, scaled=True, master=False)
     gap_plain, gap = _gap(plain, theirs), _gap(ours, theirs)
-    print(f"ERR fp16_tracking gap_unscaled={gap_plain:.4f} gap_scaled={gap:.4f} bound={0.1 * theirs[0]:.4f} guard {st} "
-          f"unscaled {[round(v, 3) for v in plain[::6]]} scaled {[round(v, 3) for v in ours[::6]]}")
+    bound = 0.1 * theirs[0]
+    kept_plain, kept = _tracked(plain, theirs, bound), _tracked(ours, theirs, bound)
+    print(f"ERR fp16_tracking gap_unscaled={gap_plain:.4f} gap_scaled={gap:.4f} bound={bound:.4f} "
+          f"tracked_unscaled={kept_plain} tracked_scaled={kept} guard {st} "
+          f"unscaled {[round(v, 3) for v in plain[:12]]} .. {[round(v, 3) for v in plain[12::6]]} "
+          f"scaled {[round(v, 3) for v in ours[:12]]} .. {[round(v, 3) for v in ours[12::6]]} "
+          f"torch {[round(v, 3) for v in theirs[:12]]}")
     assert abs(ours[0] - theirs[0]) < 0.02 * theirs[0]
-    assert gap <= gap_plain, (gap, gap_plain)
+    assert kept >= kept_plain, (kept, kept_plain)
+    assert gap <= gap_plain or not gap_plain < theirs[0], (gap, gap_plain)
     assert all(math.isfinite(v) for v in ours) and bool(torch.isfinite(params.float()).all())
     assert st["applied"] + st["skipped_total"] == TRACK_STEPS
