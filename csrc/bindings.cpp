@@ -450,43 +450,96 @@ void xent_bwd_reg_(at::Tensor logits, const at::Tensor& labels, const at::Tensor
         "xent_bwd_reg");
 }
 
-// The AdamW kernels' optional skip flag: int32[>=1] on p's device (non-zero: the launch does nothing).
-static const int* skip_flag(const at::Tensor& p, const c10::optional<at::Tensor>& skip_dev) {
-  if (!skip_dev.has_value()) return nullptr;
-  TORCH_CHECK(skip_dev->scalar_type() == at::kInt && skip_dev->numel() >= 1, "adamw: skip_dev int32");
-  same_dev(p, *skip_dev, "skip_dev");
-  return skip_dev->data_ptr<int>();
+// ---- AdamW -------------------------------------------------------------------------------------
+// Five entry points over three launchers. They share the helpers below; what each one asks of its
+// tensors beyond that (dtypes, alignment) is checked in its own body.
+
+// An optional device scalar of the AdamW kernels: `count` or more elements of T on p's device, else null.
+template <typename T>
+const T* adamw_dev_scalar(const char* what, const at::Tensor& p, const c10::optional<at::Tensor>& t, const char* name,
+                          int64_t count) {
+  if (!t.has_value()) return nullptr;
+  constexpr at::ScalarType st = c10::CppTypeToScalarType<T>::value;
+  TORCH_CHECK(t->scalar_type() == st && t->numel() >= count, what, ": ", name, " must be ", st, "[", count, "]");
+  same_dev(p, *t, name);
+  return t->data_ptr<T>();
+}
+
+// The launchers' argument block (kernels/launchers.h) from the scalars every entry point takes; sr stays
+// zero (round to nearest). gscale_dev fp32[1], hyper_dev fp64[3] = {lr, bc1, bc2_sqrt}, skip_dev int32[1]
+// (non-zero: the launch does nothing); each is optional.
+pra_adamw_args adamw_args(const char* what, const at::Tensor& p, double lr, double b1, double b2, double eps,
+                          double wd, double bc1, double bc2_sqrt, double gscale,
+                          const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev,
+                          bool fast, const c10::optional<at::Tensor>& skip_dev) {
+  pra_adamw_args a{};
+  a.lr = lr, a.b1 = b1, a.b2 = b2, a.eps = eps, a.wd = wd, a.bc1 = bc1, a.bc2_sqrt = bc2_sqrt;
+  a.gscale = (float)gscale;
+  a.fast = fast ? 1 : 0;
+  a.gscale_dev = adamw_dev_scalar<float>(what, p, gscale_dev, "gscale_dev", 1);
+  a.hyper_dev = adamw_dev_scalar<double>(what, p, hyper_dev, "hyper_dev", 3);
+  a.skip_dev = adamw_dev_scalar<int>(what, p, skip_dev, "skip_dev", 1);
+  return a;
+}
+
+// What the stochastic-rounding entry points add to the block (csrc/kernels/philox_sr.h).
+pra_sr_args sr_args(const char* what, const at::Tensor& p, uint64_t seed, int64_t base, int64_t step,
+                    const c10::optional<at::Tensor>& step_dev, int64_t mask) {
+  TORCH_CHECK(p.scalar_type() == at::kBFloat16 || p.scalar_type() == at::kHalf, what,
+              ": stochastic rounding needs bf16 or fp16 parameters and moments");
+  TORCH_CHECK(base >= 0 && base % 8 == 0, what, ": base must be >= 0 and a multiple of 8, got ", base);
+  TORCH_CHECK(mask >= 1 && mask <= 7, what, ": mask must be in 1..7, got ", mask);
+  TORCH_CHECK(step >= 0 && step <= INT32_MAX, what, ": step");
+  return pra_sr_args{seed, base, (int)step, adamw_dev_scalar<int>(what, p, step_dev, "step_dev", 1), (int)mask};
+}
+
+void check_aligned16(const char* what, std::initializer_list<at::Tensor> ts) {
+  for (const at::Tensor& t : ts)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": operands must be 16-B aligned");
+}
+
+// Flat p / g / m / v: contiguous, of one length, on p's device.
+void check_adamw_flat(const char* what, const at::Tensor& p, const at::Tensor& g, const at::Tensor& m,
+                      const at::Tensor& v) {
+  check_dev(p, "p");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), what, ": contiguous");
+  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), what, ": sizes");
+  same_dev(p, g, "grad");
+  same_dev(p, m, "exp_avg");
+  same_dev(p, v, "exp_avg_sq");
+}
+
+// The tiled kernel's matrices: contiguous [rows, cols] p / g / m / v and pt [cols, rows] of p's dtype on p's
+// device, rows and cols multiples of 64 (the tile), every pointer 16-B aligned (16-B loads and stores).
+void check_adamw_t(const char* what, const at::Tensor& p, const at::Tensor& g, const at::Tensor& m,
+                   const at::Tensor& v, const at::Tensor& pt) {
+  check_dev(p, "p");
+  TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && g.sizes() == p.sizes() && m.sizes() == p.sizes() &&
+                  v.sizes() == p.sizes() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
+              what, ": p/g/m/v must be contiguous [rows, cols]");
+  const int64_t rows = p.size(0), cols = p.size(1);
+  TORCH_CHECK(pt.dim() == 2 && pt.size(0) == cols && pt.size(1) == rows && pt.is_contiguous(), what,
+              ": pt [cols, rows]");
+  TORCH_CHECK(rows % 64 == 0 && cols % 64 == 0, what, ": rows and cols must be multiples of 64");
+  for (const at::Tensor& t : {g, m, v, pt}) {
+    same_dev(p, t, "adamw_t operand");
+    TORCH_CHECK(t.scalar_type() == p.scalar_type(), what, ": dtypes must match");
+  }
+  check_aligned16(what, {p, g, m, v, pt});
 }
 
 void adamw_flat_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, double lr, double b1, double b2,
                  double eps, double wd, double bc1, double bc2_sqrt, double gscale,
                  const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
-    const c10::optional<at::Tensor>& skip_dev) {
+                 const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_flat");
-  check_dev(p, "p");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), "adamw: contiguous");
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adamw: sizes");
+  check_adamw_flat("adamw", p, g, m, v);
   TORCH_CHECK(g.scalar_type() == p.scalar_type() && m.scalar_type() == v.scalar_type(), "adamw: dtypes");
-  same_dev(p, g, "grad");
-  same_dev(p, m, "exp_avg");
-  same_dev(p, v, "exp_avg_sq");
   const c10::DeviceGuard guard(p.device());
-  const float* gsd = nullptr;
-  if (gscale_dev.has_value()) {
-    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw: gscale_dev fp32");
-    same_dev(p, *gscale_dev, "gscale_dev");
-    gsd = gscale_dev->data_ptr<float>();
-  }
-  const double* hyd = nullptr;
-  if (hyper_dev.has_value()) {
-    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw: hyper_dev fp64[3]");
-    same_dev(p, *hyper_dev, "hyper_dev");
-    hyd = hyper_dev->data_ptr<double>();
-  }
-  const int* skd = skip_flag(p, skip_dev);
-  check(pra_adamw_flat(dt(p), dt(m), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1,
-                       b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd,
-                       hyd, fast ? 1 : 0, skd, stream_of(p)),
+  const pra_adamw_args a =
+      adamw_args("adamw", p, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, fast, skip_dev);
+  check(pra_adamw_flat(dt(p), dt(m), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), &a,
+                       stream_of(p)),
         "adamw_flat");
 }
 
@@ -494,7 +547,7 @@ void adamw_flat_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, 
 void adamw_master_(at::Tensor p, at::Tensor pm, const at::Tensor& g, at::Tensor m, at::Tensor v, double lr, double b1,
                    double b2, double eps, double wd, double bc1, double bc2_sqrt, double gscale,
                    const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
-    const c10::optional<at::Tensor>& skip_dev) {
+                   const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_master");
   check_dev(p, "p");
   TORCH_CHECK(p.is_contiguous() && pm.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
@@ -506,22 +559,10 @@ void adamw_master_(at::Tensor p, at::Tensor pm, const at::Tensor& g, at::Tensor 
               "adamw_master: fp32 master and moments");
   for (const at::Tensor& t : {pm, g, m, v}) same_dev(p, t, "adamw_master operand");
   const c10::DeviceGuard guard(p.device());
-  const float* gsd = nullptr;
-  if (gscale_dev.has_value()) {
-    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_master: gscale_dev fp32");
-    same_dev(p, *gscale_dev, "gscale_dev");
-    gsd = gscale_dev->data_ptr<float>();
-  }
-  const double* hyd = nullptr;
-  if (hyper_dev.has_value()) {
-    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_master: hyper_dev fp64[3]");
-    same_dev(p, *hyper_dev, "hyper_dev");
-    hyd = hyper_dev->data_ptr<double>();
-  }
-  const int* skd = skip_flag(p, skip_dev);
+  const pra_adamw_args a = adamw_args("adamw_master", p, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev,
+                                      hyper_dev, fast, skip_dev);
   check(pra_adamw_master(dt(p), p.data_ptr(), pm.data_ptr<float>(), g.data_ptr(), m.data_ptr<float>(),
-                         v.data_ptr<float>(), p.numel(), lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd,
-                         fast ? 1 : 0, skd, stream_of(p)),
+                         v.data_ptr<float>(), p.numel(), &a, stream_of(p)),
         "adamw_master");
 }
 
@@ -529,54 +570,16 @@ void adamw_master_(at::Tensor p, at::Tensor pm, const at::Tensor& g, at::Tensor 
 void adamw_t_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, at::Tensor pt, double lr, double b1,
               double b2, double eps, double wd, double bc1, double bc2_sqrt, double gscale,
               const c10::optional<at::Tensor>& gscale_dev, const c10::optional<at::Tensor>& hyper_dev, bool fast,
-    const c10::optional<at::Tensor>& skip_dev) {
+              const c10::optional<at::Tensor>& skip_dev) {
   const Range range_("pyrecover::adamw_t");
-  check_dev(p, "p");
-  TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && g.sizes() == p.sizes() && m.sizes() == p.sizes() &&
-                  v.sizes() == p.sizes() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
-              "adamw_t: p/g/m/v must be contiguous [rows, cols]");
-  const int64_t rows = p.size(0), cols = p.size(1);
-  TORCH_CHECK(pt.dim() == 2 && pt.size(0) == cols && pt.size(1) == rows && pt.is_contiguous(), "adamw_t: pt [cols, rows]");
-  TORCH_CHECK(rows % 64 == 0 && cols % 64 == 0, "adamw_t: rows and cols must be multiples of 64");
+  check_adamw_t("adamw_t", p, g, m, v, pt);
   TORCH_CHECK(p.element_size() == 2, "adamw_t: 16-bit parameters required");
-  for (const at::Tensor& t : {g, m, v, pt}) {
-    same_dev(p, t, "adamw_t operand");
-    TORCH_CHECK(t.scalar_type() == p.scalar_type(), "adamw_t: dtypes must match");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw_t: operands must be 16-B aligned");
-  }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0, "adamw_t: p must be 16-B aligned");
   const c10::DeviceGuard guard(p.device());
-  const float* gsd = nullptr;
-  if (gscale_dev.has_value()) {
-    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_t: gscale_dev fp32");
-    same_dev(p, *gscale_dev, "gscale_dev");
-    gsd = gscale_dev->data_ptr<float>();
-  }
-  const double* hyd = nullptr;
-  if (hyper_dev.has_value()) {
-    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_t: hyper_dev fp64[3]");
-    same_dev(p, *hyper_dev, "hyper_dev");
-    hyd = hyper_dev->data_ptr<double>();
-  }
-  const int* skd = skip_flag(p, skip_dev);
-  check(pra_adamw_t(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)rows,
-                    (int)cols, lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd,
-                    stream_of(p)),
+  const pra_adamw_args a =
+      adamw_args("adamw_t", p, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, fast, skip_dev);
+  check(pra_adamw_t(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)p.size(0),
+                    (int)p.size(1), &a, stream_of(p)),
         "adamw_t");
-}
-
-// Arguments the stochastic-rounding AdamW launches add (csrc/kernels/philox_sr.h).
-static const int* sr_args(const char* what, const at::Tensor& p, int64_t base, int64_t step, int64_t mask,
-                          const c10::optional<at::Tensor>& step_dev) {
-  TORCH_CHECK(p.scalar_type() == at::kBFloat16 || p.scalar_type() == at::kHalf, what,
-              ": stochastic rounding needs bf16 or fp16 parameters and moments");
-  TORCH_CHECK(base >= 0 && base % 8 == 0, what, ": base must be >= 0 and a multiple of 8, got ", base);
-  TORCH_CHECK(mask >= 1 && mask <= 7, what, ": mask must be in 1..7, got ", mask);
-  TORCH_CHECK(step >= 0 && step <= INT32_MAX, what, ": step");
-  if (!step_dev.has_value()) return nullptr;
-  TORCH_CHECK(step_dev->scalar_type() == at::kInt && step_dev->numel() >= 1, what, ": step_dev int32");
-  same_dev(p, *step_dev, "step_dev");
-  return step_dev->data_ptr<int>();
 }
 
 // adamw_flat_ for 16-bit state with the tensors in `mask` (bit 0 p, 1 exp_avg, 2 exp_avg_sq) rounded
@@ -587,34 +590,17 @@ void adamw_flat_sr_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor 
                     const c10::optional<at::Tensor>& skip_dev, uint64_t seed, int64_t base, int64_t step,
                     const c10::optional<at::Tensor>& step_dev, int64_t mask) {
   const Range range_("pyrecover::adamw_flat_sr");
-  check_dev(p, "p");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(), "adamw_sr: contiguous");
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel() && p.numel() == v.numel(), "adamw_sr: sizes");
+  check_adamw_flat("adamw_sr", p, g, m, v);
   TORCH_CHECK(g.scalar_type() == p.scalar_type() && m.scalar_type() == p.scalar_type() &&
                   v.scalar_type() == p.scalar_type(), "adamw_sr: dtypes must match");
-  same_dev(p, g, "grad");
-  same_dev(p, m, "exp_avg");
-  same_dev(p, v, "exp_avg_sq");
-  const int* std_ = sr_args("adamw_flat_sr", p, base, step, mask, step_dev);
-  for (const at::Tensor& t : {p, g, m, v})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw_flat_sr: operands must be 16-B aligned");
+  const pra_sr_args sr = sr_args("adamw_flat_sr", p, seed, base, step, step_dev, mask);
+  check_aligned16("adamw_flat_sr", {p, g, m, v});
   const c10::DeviceGuard guard(p.device());
-  const float* gsd = nullptr;
-  if (gscale_dev.has_value()) {
-    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_sr: gscale_dev fp32");
-    same_dev(p, *gscale_dev, "gscale_dev");
-    gsd = gscale_dev->data_ptr<float>();
-  }
-  const double* hyd = nullptr;
-  if (hyper_dev.has_value()) {
-    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_sr: hyper_dev fp64[3]");
-    same_dev(p, *hyper_dev, "hyper_dev");
-    hyd = hyper_dev->data_ptr<double>();
-  }
-  const int* skd = skip_flag(p, skip_dev);
-  check(pra_adamw_flat_sr(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, b1, b2, eps,
-                          wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd, seed, base, (int)step, std_,
-                          (int)mask, stream_of(p)),
+  pra_adamw_args a =
+      adamw_args("adamw_sr", p, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, fast, skip_dev);
+  a.sr = sr;
+  check(pra_adamw_flat(dt(p), dt(m), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), &a,
+                       stream_of(p)),
         "adamw_flat_sr");
 }
 
@@ -625,38 +611,14 @@ void adamw_t_sr_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, 
                  const c10::optional<at::Tensor>& skip_dev, uint64_t seed, int64_t base, int64_t step,
                  const c10::optional<at::Tensor>& step_dev, int64_t mask) {
   const Range range_("pyrecover::adamw_t_sr");
-  check_dev(p, "p");
-  TORCH_CHECK(p.dim() == 2 && p.is_contiguous() && g.sizes() == p.sizes() && m.sizes() == p.sizes() &&
-                  v.sizes() == p.sizes() && g.is_contiguous() && m.is_contiguous() && v.is_contiguous(),
-              "adamw_t_sr: p/g/m/v must be contiguous [rows, cols]");
-  const int64_t rows = p.size(0), cols = p.size(1);
-  TORCH_CHECK(pt.dim() == 2 && pt.size(0) == cols && pt.size(1) == rows && pt.is_contiguous(),
-              "adamw_t_sr: pt [cols, rows]");
-  TORCH_CHECK(rows % 64 == 0 && cols % 64 == 0, "adamw_t_sr: rows and cols must be multiples of 64");
-  for (const at::Tensor& t : {g, m, v, pt}) {
-    same_dev(p, t, "adamw_t_sr operand");
-    TORCH_CHECK(t.scalar_type() == p.scalar_type(), "adamw_t_sr: dtypes must match");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw_t_sr: operands must be 16-B aligned");
-  }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0, "adamw_t_sr: p must be 16-B aligned");
-  const int* std_ = sr_args("adamw_t_sr", p, base, step, mask, step_dev);
+  check_adamw_t("adamw_t_sr", p, g, m, v, pt);
+  const pra_sr_args sr = sr_args("adamw_t_sr", p, seed, base, step, step_dev, mask);
   const c10::DeviceGuard guard(p.device());
-  const float* gsd = nullptr;
-  if (gscale_dev.has_value()) {
-    TORCH_CHECK(gscale_dev->scalar_type() == at::kFloat && gscale_dev->numel() >= 1, "adamw_t_sr: gscale_dev fp32");
-    same_dev(p, *gscale_dev, "gscale_dev");
-    gsd = gscale_dev->data_ptr<float>();
-  }
-  const double* hyd = nullptr;
-  if (hyper_dev.has_value()) {
-    TORCH_CHECK(hyper_dev->scalar_type() == at::kDouble && hyper_dev->numel() >= 3, "adamw_t_sr: hyper_dev fp64[3]");
-    same_dev(p, *hyper_dev, "hyper_dev");
-    hyd = hyper_dev->data_ptr<double>();
-  }
-  const int* skd = skip_flag(p, skip_dev);
-  check(pra_adamw_t_sr(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)rows,
-                       (int)cols, lr, b1, b2, eps, wd, bc1, bc2_sqrt, (float)gscale, gsd, hyd, fast ? 1 : 0, skd, seed,
-                       base, (int)step, std_, (int)mask, stream_of(p)),
+  pra_adamw_args a =
+      adamw_args("adamw_t_sr", p, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, fast, skip_dev);
+  a.sr = sr;
+  check(pra_adamw_t(dt(p), p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), pt.data_ptr(), (int)p.size(0),
+                    (int)p.size(1), &a, stream_of(p)),
         "adamw_t_sr");
 }
 
@@ -1182,28 +1144,24 @@ PYBIND11_MODULE(_C, m) {
   m.def("xent_fwd_reg", &xent_fwd_reg);
   m.def("xent_bwd_reg_", &xent_bwd_reg_);
   namespace py = pybind11;
-  m.def("adamw_flat_", &adamw_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"),
-        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
-        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false, py::arg("skip_dev") = py::none());
-  m.def("adamw_t_", &adamw_t_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("pt"), py::arg("lr"),
-        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
-        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false, py::arg("skip_dev") = py::none());
-  m.def("adamw_flat_sr_", &adamw_flat_sr_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"),
-        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
-        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false, py::arg("skip_dev") = py::none(), py::kw_only(), py::arg("seed"), py::arg("base"),
-        py::arg("step"), py::arg("step_dev") = py::none(), py::arg("mask"));
+  // the scalars every AdamW entry point takes after its tensors, and what the stochastic-rounding ones add
+#define PRA_ADAMW_PYARGS                                                                                          \
+  py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"), \
+      py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),                   \
+      py::arg("fast") = false, py::arg("skip_dev") = py::none()
+#define PRA_ADAMW_SR_PYARGS \
+  py::kw_only(), py::arg("seed"), py::arg("base"), py::arg("step"), py::arg("step_dev") = py::none(), py::arg("mask")
+  m.def("adamw_flat_", &adamw_flat_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), PRA_ADAMW_PYARGS);
+  m.def("adamw_t_", &adamw_t_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("pt"),
+        PRA_ADAMW_PYARGS);
+  m.def("adamw_flat_sr_", &adamw_flat_sr_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), PRA_ADAMW_PYARGS,
+        PRA_ADAMW_SR_PYARGS);
   m.def("adamw_t_sr_", &adamw_t_sr_, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("pt"),
-        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
-        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false, py::arg("skip_dev") = py::none(), py::kw_only(), py::arg("seed"), py::arg("base"),
-        py::arg("step"), py::arg("step_dev") = py::none(), py::arg("mask"));
-  m.def("adamw_master_", &adamw_master_,py::arg("p"), py::arg("pm"), py::arg("g"), py::arg("m"), py::arg("v"),
-        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("bc1"), py::arg("bc2_sqrt"),
-        py::arg("gscale"), py::arg("gscale_dev") = py::none(), py::arg("hyper_dev") = py::none(),
-        py::arg("fast") = false, py::arg("skip_dev") = py::none());
+        PRA_ADAMW_PYARGS, PRA_ADAMW_SR_PYARGS);
+  m.def("adamw_master_", &adamw_master_, py::arg("p"), py::arg("pm"), py::arg("g"), py::arg("m"), py::arg("v"),
+        PRA_ADAMW_PYARGS);
+#undef PRA_ADAMW_PYARGS
+#undef PRA_ADAMW_SR_PYARGS
   m.def("grad_norm", &grad_norm);
   m.def("guard_step_", &guard_step_, py::arg("x"), py::arg("sq"), py::arg("state"), py::arg("out"), py::arg("hyper"),
         py::arg("max_norm"), py::arg("pre_scale"), py::arg("dynamic"), py::arg("interval"), py::arg("b1"),

@@ -67,15 +67,35 @@ hipError_t pra_xent_bwd_reg(int dtype, void* logits, const int64_t* labels, cons
                             const float* grad_out, long T, long V, long ld, long ignore_index, double z_loss,
                             double label_smoothing, hipStream_t s);
 
-hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n, double lr,
-                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-    hipStream_t s);
+// Stochastic rounding of a 16-bit AdamW launch (philox_sr.h). mask 0: round to nearest, the rest is unused.
+typedef struct pra_sr_args {
+  unsigned long long seed;  // Philox key
+  long long base;           // flat position of the launch's first element (>= 0, % 8 == 0)
+  int step;                 // AdamW step number (1-based: the one the bias corrections use) ...
+  const int* step_dev;      // ... or, when non-null, read from device memory (guard / graph mode)
+  int mask;                 // bit 0: round p stochastically, bit 1: exp_avg, bit 2: exp_avg_sq
+} pra_sr_args;
+// Everything launch-uniform of an AdamW update (optim.hip documents the math and the device scalars).
+// The launchers copy the block before they return and keep no pointer to it (graph capture).
+typedef struct pra_adamw_args {
+  double lr, b1, b2, eps, wd, bc1, bc2_sqrt;
+  float gscale;             // gradient multiplier, times gscale_dev[0] when that is non-null
+  int fast;                 // hardware reciprocal / square root instead of torch's exact expression tree
+  const float* gscale_dev;  // optional device scalars: fp32[1],
+  const double* hyper_dev;  //   fp64[3] = {lr, bc1, bc2_sqrt} replacing the host values,
+  const int* skip_dev;      //   int32[1], non-zero: the launch does nothing
+  pra_sr_args sr;           // non-zero mask: 16-bit state only, not the master launcher
+} pra_adamw_args;
+// pdtype: param/grad dtype; sdtype: moment dtype (the same: all fp32 or all one 16-bit type)
+hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n,
+                          const pra_adamw_args* args, hipStream_t s);
 // fp32-master AdamW: updates pm / m / v (fp32) and writes p = round(pm) (16-bit params)
-hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n, double lr,
-                            double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                            const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-    hipStream_t s);
+hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n,
+                            const pra_adamw_args* args, hipStream_t s);
+// AdamW of one row-major [rows, cols] matrix that also writes pt = p^T [cols, rows] (rows, cols % 64 == 0,
+// 16-bit p / g / m / v / pt of one dtype); with sr.mask, pt takes the rounded p
+hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols,
+                       const pra_adamw_args* args, hipStream_t s);
 int pra_sumsq_partials();
 hipError_t pra_grad_norm(int dtype, const void* x, long n, float* ws, float* out, float max_norm, float pre_scale,
                          hipStream_t s);
@@ -97,23 +117,6 @@ hipError_t pra_pull_gather(const void* const* srcs, void* const* dsts, const lon
 // int64 entries: phase 1 reduces the union rows rank `me` owns into grads[me], phase 2 copies the others
 hipError_t pra_sparse_rows(int dtype, int phase, void* const* grads, const int64_t* const* ids, int W, int me, long n,
                            long V, long D, hipStream_t s);
-
-hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
-                       double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                       const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-    hipStream_t s);
-// Stochastic rounding of 16-bit p / exp_avg / exp_avg_sq (philox_sr.h): mask bit 0 / 1 / 2; base: flat
-// position of the first element (>= 0, % 8 == 0); step_dev (device int32), when non-null, replaces step
-hipError_t pra_adamw_flat_sr(int dtype, void* p, const void* g, void* m, void* v, long n, double lr, double b1,
-                             double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                             const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-                             unsigned long long seed, long long base, int step, const int* step_dev, int mask,
-                             hipStream_t s);
-hipError_t pra_adamw_t_sr(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
-                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-                          unsigned long long seed, long long base, int step, const int* step_dev, int mask,
-                          hipStream_t s);
 
 hipError_t pra_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
                         int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal,

@@ -21,10 +21,17 @@
 // non-null and non-zero in device memory, makes the launch a no-op (train.py --loss-scale: the step's
 // gradient is not finite, guard_finish_kernel below); a zero multiplier alone would still decay the
 // weights and the moments. A null `skip_dev` is the unguarded path.
+//
+// All of these reach the launchers as one block, pra_adamw_args (launchers.h).
+#include <type_traits>
+
 #include "common.h"
+#include "launchers.h"
 #include "philox_sr.h"
 
 namespace pra {
+
+using SrArgs = ::pra_sr_args;
 
 // Scalars of one update, prepared once per thread from the host (or device, graph mode) values.
 struct AdamCoef {
@@ -54,6 +61,9 @@ __device__ __forceinline__ AdamCoef adam_coef(double lr, double b1, double b2, d
   c.epsf = (float)eps;
   c.rbc2 = __builtin_amdgcn_rcpf(c.bc2f);
   return c;
+}
+__device__ __forceinline__ AdamCoef adam_coef(const pra_adamw_args& a) {
+  return adam_coef(a.lr, a.b1, a.b2, a.eps, a.wd, a.bc1, a.bc2_sqrt, a.hyper_dev);
 }
 
 // One AdamW element update with every fused multiply-add written out, so all kernels that use it
@@ -146,10 +156,17 @@ __device__ __forceinline__ pra_u32x4 pack8(const float (&v)[8]) {
   }
 }
 
-template <typename P, typename S, bool FAST>
-__global__ __launch_bounds__(256) void adamw_kernel(P* __restrict__ p, const P* __restrict__ g, S* __restrict__ m,
-                                                    S* __restrict__ v, long n, double lr, double b1, double b2,
-                                                    double eps, double wd, double bc1, double bc2_sqrt, float gscale,
+// Flat AdamW of fp32 parameters, gradients and moments.
+// This kernel and adamw_master_kernel keep their scalars as separate parameters: the three optional
+// pointers are `noalias` only as kernel parameters, not as members of a by-value block, and without it
+// the compiler schedules these two loops differently (exact math: 82 -> 62-64 VGPRs, occupancy 5 -> 8;
+// fast master: 56 -> 62-64 VGPRs; profiles/adamw_args/). The two 16-bit kernels below compile to the same
+// registers and occupancy either way and take the block.
+template <bool FAST>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, long n, double lr,
+                                                    double b1, double b2, double eps, double wd, double bc1,
+                                                    double bc2_sqrt, float gscale,
                                                     const float* __restrict__ gscale_dev,
                                                     const double* __restrict__ hyper_dev,
                                                     const int* __restrict__ skip_dev) {
@@ -160,23 +177,23 @@ __global__ __launch_bounds__(256) void adamw_kernel(P* __restrict__ p, const P* 
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
     const long o = i * 8;
     float pv[8], gv[8], mv[8], vv[8];
-    load8<P>(p + o, pv);
-    load8<P>(g + o, gv);
-    load8<S>(m + o, mv);
-    load8<S>(v + o, vv);
+    load8<float>(p + o, pv);
+    load8<float>(g + o, gv);
+    load8<float>(m + o, mv);
+    load8<float>(v + o, vv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) adamw_elem<FAST>(pv[j], mv[j], vv[j], gv[j], gs, c);
-    store8<P>(p + o, pv);
-    store8<S>(m + o, mv);
-    store8<S>(v + o, vv);
+    store8<float>(p + o, pv);
+    store8<float>(m + o, mv);
+    store8<float>(v + o, vv);
   }
   // tail
   for (long o = n8 * 8 + (long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long)gridDim.x * 256) {
-    float pv = to_f<P>(p[o]), mv = to_f<S>(m[o]), vv = to_f<S>(v[o]);
-    adamw_elem<FAST>(pv, mv, vv, to_f<P>(g[o]), gs, c);
-    p[o] = from_f<P>(pv);
-    m[o] = from_f<S>(mv);
-    v[o] = from_f<S>(vv);
+    float pv = p[o], mv = m[o], vv = v[o];
+    adamw_elem<FAST>(pv, mv, vv, g[o], gs, c);
+    p[o] = pv;
+    m[o] = mv;
+    v[o] = vv;
   }
 }
 
@@ -205,18 +222,15 @@ __device__ __forceinline__ P from_f_sr(float x, bool sr_on, const SrArgs& sr, lo
 
 // Flat 16-bit AdamW (p, g, m, v of one dtype): U chunks of 8 per thread, all their loads issued
 // before the math (more bytes in flight per wave), non-temporal. Same math as adamw_kernel.
-// SR (pra_adamw_flat_sr): the tensors in sr.mask are rounded stochastically (philox_sr.h) from the
+// SR (a non-zero sr.mask): the tensors in sr.mask are rounded stochastically (philox_sr.h) from the
 // same fp32 adamw_elem results; element o of the launch is flat position sr.base + o.
-template <typename P, bool FAST, int U, bool SR = false>
+template <typename P, bool FAST, int U, bool SR>
 __global__ __launch_bounds__(256) void adamw16_kernel(P* __restrict__ p, const P* __restrict__ g, P* __restrict__ m,
-                                                      P* __restrict__ v, long n, double lr, double b1, double b2,
-                                                      double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                                                      const float* __restrict__ gscale_dev,
-                                                      const double* __restrict__ hyper_dev,
-                                                      const int* __restrict__ skip_dev, SrArgs sr) {
-  if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
-  const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
-  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
+                                                      P* __restrict__ v, long n, pra_adamw_args a) {
+  if (a.skip_dev && *a.skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
+  const float gs = a.gscale_dev ? a.gscale * a.gscale_dev[0] : a.gscale;
+  const AdamCoef c = adam_coef(a);
+  const SrArgs& sr = a.sr;
   [[maybe_unused]] const uint32_t t = SR ? (uint32_t)(sr.step_dev ? *sr.step_dev : sr.step) : 0u;
   const long n8 = n / 8, stride = (long)gridDim.x * 256 * U;
   for (long i0 = (long)blockIdx.x * 256 * U + threadIdx.x; i0 < n8; i0 += stride) {
@@ -275,7 +289,7 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(P* __restrict__ p, fl
                                                            double bc2_sqrt, float gscale,
                                                            const float* __restrict__ gscale_dev,
                                                            const double* __restrict__ hyper_dev,
-                                                    const int* __restrict__ skip_dev) {
+                                                           const int* __restrict__ skip_dev) {
   if (skip_dev && *skip_dev != 0) return;  // non-finite gradient (guard_finish_kernel): nothing is read or written
   const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
   const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
@@ -309,22 +323,19 @@ __global__ __launch_bounds__(256) void adamw_master_kernel(P* __restrict__ p, fl
 // updated values it already holds: the separate transpose pass re-read the whole model after
 // every update (13.5 GB/step at 7B). Block = one 64 x 64 tile; the updated p tile goes through
 // LDS (padded rows) to 16-B transposed stores. Same math and rounding as adamw_kernel.
-// SR (pra_adamw_t_sr): as adamw16_kernel's; element (r, c) is flat position sr.base + r * cols + c, and
+// SR: as adamw16_kernel's; element (r, c) is flat position sr.base + r * cols + c, and
 // the shadow takes the same rounded p, so this stays bitwise equal to the flat kernel plus a transpose.
-template <typename P, bool FAST, int TILE, bool NT, bool SR = false>
+template <typename P, bool FAST, int TILE, bool NT, bool SR>
 __global__ __launch_bounds__(256) void adamw_t_kernel(P* __restrict__ p, const P* __restrict__ g, P* __restrict__ m,
                                                       P* __restrict__ v, P* __restrict__ pt, int rows, int cols,
-                                                      double lr, double b1, double b2, double eps, double wd,
-                                                      double bc1, double bc2_sqrt, float gscale,
-                                                      const float* __restrict__ gscale_dev,
-                                                      const double* __restrict__ hyper_dev,
-                                                      const int* __restrict__ skip_dev, SrArgs sr) {
+                                                      pra_adamw_args a) {
   constexpr int CH = TILE / 8;            // 8-element chunks per tile row
   constexpr int PASSES = TILE * CH / 256;  // chunks per thread
   __shared__ uint16_t tile[TILE][TILE + 8];
-  if (skip_dev && *skip_dev != 0) return;  // block-uniform, before the barrier below
-  const float gs = gscale_dev ? gscale * gscale_dev[0] : gscale;
-  const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, bc1, bc2_sqrt, hyper_dev);
+  if (a.skip_dev && *a.skip_dev != 0) return;  // block-uniform, before the barrier below
+  const float gs = a.gscale_dev ? a.gscale * a.gscale_dev[0] : a.gscale;
+  const AdamCoef c = adam_coef(a);
+  const SrArgs& sr = a.sr;
   [[maybe_unused]] const uint32_t t = SR ? (uint32_t)(sr.step_dev ? *sr.step_dev : sr.step) : 0u;
   const long r0 = (long)blockIdx.y * TILE, c0 = (long)blockIdx.x * TILE;
 #pragma unroll
@@ -465,155 +476,103 @@ __global__ __launch_bounds__(256) void guard_finish_kernel(const float* __restri
   }
 }
 
+// The launchers' choice of an instantiation: f(std::bool_constant<flag>{}...), one per runtime flag.
+template <bool... Bs, typename F>
+hipError_t with_flags(F&& f) {
+  return f(std::bool_constant<Bs>{}...);
+}
+template <bool... Bs, typename F, typename... Rest>
+hipError_t with_flags(F&& f, bool flag, Rest... rest) {
+  return flag ? with_flags<Bs..., true>(f, rest...) : with_flags<Bs..., false>(f, rest...);
+}
+
+// Grid of a flat launch over n elements whose blocks take `chunks` 8-element chunks per trip: 1 to 4096
+// blocks (beyond that the kernels' loops take further trips).
+inline dim3 flat_grid(long n, long chunks) {
+  const long nb = (n / 8 + chunks - 1) / chunks;
+  return dim3((unsigned)(nb > 4096 ? 4096 : nb < 1 ? 1 : nb));
+}
+
+// Round-to-nearest (mask 0), or a stochastic-rounding launch the kernels can index.
+inline bool sr_valid(const SrArgs& sr) {
+  return sr.mask == 0 || (sr.base >= 0 && sr.base % 8 == 0 && sr.mask >= 1 && sr.mask <= 7);
+}
+
 }  // namespace pra
 
 extern "C" {
 
-// pdtype: param/grad dtype; sdtype: moment dtype
-hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n, double lr,
-                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
-  long blocks = (n / 8 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  if (pdtype != sdtype) return hipErrorInvalidValue;
+// The launchers copy *args: the kernels take the block by value, and nothing points to the caller's
+// copy once a launcher has returned.
+
+// pdtype: param/grad dtype; sdtype: moment dtype. args->sr.mask: 16-bit state only; the tensors in the mask
+// (bit 0 p, bit 1 exp_avg, bit 2 exp_avg_sq) are rounded stochastically, the rest is stored as without it.
+hipError_t pra_adamw_flat(int pdtype, int sdtype, void* p, const void* g, void* m, void* v, long n,
+                          const pra_adamw_args* args, hipStream_t s) {
+  const pra_adamw_args a = *args;
+  if (pdtype != sdtype || !pra::sr_valid(a.sr)) return hipErrorInvalidValue;
+  if (a.sr.mask && (pdtype == ::pra::kF32 || n < 0)) return hipErrorInvalidValue;
   if (pdtype != ::pra::kF32) {
     // 16-bit: two iterations per thread, non-temporal (Llama-3-8B-shape matrices in isolation 4.82 ->
     // 5.28-5.46 TB/s; 8B B1 step -0.76%: profiles/r6/adamw/)
-    long nb = (n / 8 + 511) / 512;
-    if (nb > 4096) nb = 4096;
-    if (nb < 1) nb = 1;
-    if (fast) {
-      PRA_DISPATCH_16BIT(pdtype, T,
-                         hipLaunchKernelGGL((pra::adamw16_kernel<T, true, 2>), dim3(nb), dim3(256), 0, s, (T*)p,
-                                            (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                            gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}));
-    } else {
-      PRA_DISPATCH_16BIT(pdtype, T,
-                         hipLaunchKernelGGL((pra::adamw16_kernel<T, false, 2>), dim3(nb), dim3(256), 0, s,
-                                            (T*)p, (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt,
-                                            gscale, gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}));
-    }
-    return hipGetLastError();
+    return pra::with_flags(
+        [&](auto fast, auto sr) -> hipError_t {
+          PRA_DISPATCH_16BIT(pdtype, T,
+                             hipLaunchKernelGGL((pra::adamw16_kernel<T, fast(), 2, sr()>), pra::flat_grid(n, 512),
+                                                dim3(256), 0, s, (T*)p, (const T*)g, (T*)m, (T*)v, n, a));
+          return hipGetLastError();
+        },
+        a.fast != 0, a.sr.mask != 0);
   }
   // fp32 parameters and moments
-  if (fast) {
-    hipLaunchKernelGGL((pra::adamw_kernel<float, float, true>), dim3(blocks), dim3(256), 0, s, (float*)p,
-                       (const float*)g, (float*)m, (float*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev,
-                       hyper_dev, skip_dev);
-  } else {
-    hipLaunchKernelGGL((pra::adamw_kernel<float, float, false>), dim3(blocks), dim3(256), 0, s, (float*)p,
-                       (const float*)g, (float*)m, (float*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale, gscale_dev,
-                       hyper_dev, skip_dev);
-  }
-  return hipGetLastError();
+  return pra::with_flags(
+      [&](auto fast) -> hipError_t {
+        hipLaunchKernelGGL((pra::adamw_kernel<fast()>), pra::flat_grid(n, 256), dim3(256), 0, s, (float*)p,
+                           (const float*)g, (float*)m, (float*)v, n, a.lr, a.b1, a.b2, a.eps, a.wd, a.bc1, a.bc2_sqrt,
+                           a.gscale, a.gscale_dev, a.hyper_dev, a.skip_dev);
+        return hipGetLastError();
+      },
+      a.fast != 0);
 }
 
 // AdamW of one [rows, cols] matrix + its transposed copy pt [cols, rows] (rows, cols % 64 == 0;
 // 16-bit params, moments of the same dtype): 128 x 128 tiles where both dims allow, else 64 x 64;
 // non-temporal (Llama-3-8B B1 with shadows -1.03%, 7B B16 within noise: profiles/r6/adamw/).
-hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
-                       double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                       const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
-  if (rows % 64 || cols % 64 || rows <= 0 || cols <= 0) return hipErrorInvalidValue;
+// args->sr: as pra_adamw_flat's, base the flat position of p[0][0]; pt takes the rounded p.
+hipError_t pra_adamw_t(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols,
+                       const pra_adamw_args* args, hipStream_t s) {
+  const pra_adamw_args a = *args;
+  if (rows % 64 || cols % 64 || rows <= 0 || cols <= 0 || !pra::sr_valid(a.sr)) return hipErrorInvalidValue;
   // (A strip kernel walking 4 tiles per block was faster in isolation, 22.7 -> 21.3 ms per 7B step,
   // but slower overlapped with the backward GEMMs on the side stream: 1074.5 vs 1069.6 ms/step,
   // profiles/adamw_t_strip_ab_r2.log. Removed.)
-  const int tile = (rows % 128 == 0 && cols % 128 == 0) ? 128 : 64;
-  const dim3 grid(cols / tile, rows / tile);
-#define PRA_ADAMW_T(FASTV, TILEV)                                                                              \
-  PRA_DISPATCH_16BIT(dtype, T,                                                                                  \
-                     hipLaunchKernelGGL((pra::adamw_t_kernel<T, FASTV, TILEV, true>), grid, dim3(256), 0, s,    \
-                                        (T*)p, (const T*)g, (T*)m, (T*)v, (T*)pt, rows, cols, lr, b1, b2, eps,   \
-                                        wd, bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev, pra::SrArgs{}))
-  if (tile == 128 && fast) {
-    PRA_ADAMW_T(true, 128);
-  } else if (tile == 128) {
-    PRA_ADAMW_T(false, 128);
-  } else if (fast) {
-    PRA_ADAMW_T(true, 64);
-  } else {
-    PRA_ADAMW_T(false, 64);
-  }
-#undef PRA_ADAMW_T
-  return hipGetLastError();
+  return pra::with_flags(
+      [&](auto fast, auto big, auto sr) -> hipError_t {
+        constexpr int tile = big() ? 128 : 64;
+        PRA_DISPATCH_16BIT(dtype, T,
+                           hipLaunchKernelGGL((pra::adamw_t_kernel<T, fast(), tile, true, sr()>),
+                                              dim3(cols / tile, rows / tile), dim3(256), 0, s, (T*)p, (const T*)g,
+                                              (T*)m, (T*)v, (T*)pt, rows, cols, a));
+        return hipGetLastError();
+      },
+      a.fast != 0, rows % 128 == 0 && cols % 128 == 0, a.sr.mask != 0);
 }
 
-// Stochastic-rounding AdamW (philox_sr.h): pra_adamw_flat's 16-bit kernel with the tensors in `mask`
-// (bit 0 p, bit 1 exp_avg, bit 2 exp_avg_sq) rounded stochastically; the rest is stored as pra_adamw_flat
-// stores it. base: flat position of p[0] (>= 0, % 8 == 0); step_dev (int32, device), when non-null,
-// replaces step. 16-bit p / g / m / v of one dtype only.
-hipError_t pra_adamw_flat_sr(int dtype, void* p, const void* g, void* m, void* v, long n, double lr, double b1,
-                             double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                             const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-                             unsigned long long seed, long long base, int step, const int* step_dev, int mask,
-                             hipStream_t s) {
-  if (base < 0 || base % 8 || mask < 1 || mask > 7 || n < 0) return hipErrorInvalidValue;
-  long nb = (n / 8 + 511) / 512;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  const pra::SrArgs sr{seed, base, step, step_dev, mask};
-  if (fast) {
-    PRA_DISPATCH_16BIT(dtype, T,
-                       hipLaunchKernelGGL((pra::adamw16_kernel<T, true, 2, true>), dim3(nb), dim3(256), 0, s, (T*)p,
-                                          (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev, skip_dev, sr));
-  } else {
-    PRA_DISPATCH_16BIT(dtype, T,
-                       hipLaunchKernelGGL((pra::adamw16_kernel<T, false, 2, true>), dim3(nb), dim3(256), 0, s, (T*)p,
-                                          (const T*)g, (T*)m, (T*)v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev, skip_dev, sr));
-  }
-  return hipGetLastError();
-}
-
-// pra_adamw_t with stochastic rounding; base: flat position of p[0][0]. pt takes the rounded p.
-hipError_t pra_adamw_t_sr(int dtype, void* p, const void* g, void* m, void* v, void* pt, int rows, int cols, double lr,
-                          double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                          const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev,
-                          unsigned long long seed, long long base, int step, const int* step_dev, int mask,
-                          hipStream_t s) {
-  if (rows % 64 || cols % 64 || rows <= 0 || cols <= 0) return hipErrorInvalidValue;
-  if (base < 0 || base % 8 || mask < 1 || mask > 7) return hipErrorInvalidValue;
-  const int tile = (rows % 128 == 0 && cols % 128 == 0) ? 128 : 64;
-  const dim3 grid(cols / tile, rows / tile);
-  const pra::SrArgs sr{seed, base, step, step_dev, mask};
-#define PRA_ADAMW_T_SR(FASTV, TILEV)                                                                               \
-  PRA_DISPATCH_16BIT(dtype, T,                                                                                     \
-                     hipLaunchKernelGGL((pra::adamw_t_kernel<T, FASTV, TILEV, true, true>), grid, dim3(256), 0, s, \
-                                        (T*)p, (const T*)g, (T*)m, (T*)v, (T*)pt, rows, cols, lr, b1, b2, eps, wd,  \
-                                        bc1, bc2_sqrt, gscale, gscale_dev, hyper_dev, skip_dev, sr))
-  if (tile == 128 && fast) {
-    PRA_ADAMW_T_SR(true, 128);
-  } else if (tile == 128) {
-    PRA_ADAMW_T_SR(false, 128);
-  } else if (fast) {
-    PRA_ADAMW_T_SR(true, 64);
-  } else {
-    PRA_ADAMW_T_SR(false, 64);
-  }
-#undef PRA_ADAMW_T_SR
-  return hipGetLastError();
-}
-
-hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n, double lr,
-                            double b1, double b2, double eps, double wd, double bc1, double bc2_sqrt, float gscale,
-                            const float* gscale_dev, const double* hyper_dev, int fast, const int* skip_dev, hipStream_t s) {
-  long blocks = (n / 8 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  if (fast) {
-    PRA_DISPATCH_16BIT(pdtype, T,
-                       hipLaunchKernelGGL((pra::adamw_master_kernel<T, true>), dim3(blocks), dim3(256), 0, s, (T*)p,
-                                          pm, (const T*)g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev, skip_dev));
-  } else {
-    PRA_DISPATCH_16BIT(pdtype, T,
-                       hipLaunchKernelGGL((pra::adamw_master_kernel<T, false>), dim3(blocks), dim3(256), 0, s, (T*)p,
-                                          pm, (const T*)g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale,
-                                          gscale_dev, hyper_dev, skip_dev));
-  }
-  return hipGetLastError();
+// fp32 master and moments: there is nothing 16-bit to round stochastically but p, which is the master rounded
+// to nearest, so a non-zero args->sr.mask is an error.
+hipError_t pra_adamw_master(int pdtype, void* p, float* pm, const void* g, float* m, float* v, long n,
+                            const pra_adamw_args* args, hipStream_t s) {
+  const pra_adamw_args a = *args;
+  if (a.sr.mask) return hipErrorInvalidValue;
+  return pra::with_flags(
+      [&](auto fast) -> hipError_t {
+        PRA_DISPATCH_16BIT(pdtype, T,
+                           hipLaunchKernelGGL((pra::adamw_master_kernel<T, fast()>), pra::flat_grid(n, 256), dim3(256),
+                                              0, s, (T*)p, pm, (const T*)g, m, v, n, a.lr, a.b1, a.b2, a.eps, a.wd,
+                                              a.bc1, a.bc2_sqrt, a.gscale, a.gscale_dev, a.hyper_dev, a.skip_dev));
+        return hipGetLastError();
+      },
+      a.fast != 0);
 }
 
 int pra_sumsq_partials() { return 1024; }

@@ -20,15 +20,7 @@
 
 namespace pra {
 
-// Launch-uniform arguments of a stochastic-rounding AdamW launch (all zero: unused).
-struct SrArgs {
-  unsigned long long seed;  // Philox key
-  long long base;           // flat position of the launch's first element (>= 0, % 8 == 0)
-  int step;                 // AdamW step number (1-based: the one the bias corrections use) ...
-  const int* step_dev;      // ... or, when non-null, read from device memory (guard / graph mode)
-  int mask;                 // bit 0: round p stochastically, bit 1: exp_avg, bit 2: exp_avg_sq
-};
-
+// (The launch-uniform arguments of a stochastic-rounding launch are launchers.h's pra_sr_args.)
 enum : uint32_t { kSrStreamP = 0, kSrStreamM = 1, kSrStreamV = 2 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

@@ -330,73 +330,51 @@ class FlatAdamW(torch.optim.AdamW):
             self._step_reference(lr, b1, b2, eps, wd, bc1, bc2_sqrt, lo, hi)
             return
         C = _ext.require_for(f.data)
-        args = (lr, b1, b2, eps, wd, bc1, bc2_sqrt, self.grad_scale, self.grad_scale_dev, self.hyper)
+        # the last one is skip_dev: None is the kernels' unguarded path
+        args = (lr, b1, b2, eps, wd, bc1, bc2_sqrt, self.grad_scale, self.grad_scale_dev, self.hyper, FAST_MATH,
+                self.guard.skip_dev if self.guard is not None else None)
         m, v = self.exp_avg, self.exp_avg_sq
-
-        # (fast, skip_dev): a null skip_dev is the kernels' unguarded path
-        tail = (FAST_MATH, self.guard.skip_dev) if self.guard is not None else (FAST_MATH,)
         sharded = self._sharded()
-        if self.sr_mask:
-            # stochastic rounding: the same walk as below through the SR launches, every slice with its
-            # flat position, so the bits do not depend on how the range is cut
-            def flat_sr(a, b):
-                if a < b:
-                    C.adamw_flat_sr_(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, *tail, **self._sr_kwargs(a))
-
-            if sharded:
-                flat_sr(lo, hi)
-                return
-            cur, rest = lo, []
-            for o, rows, cols in (f.transposed_in(lo, hi) if FUSED_T else []):
-                n = rows * cols
-                if o + n > hi:
-                    rest.append(o)
-                    continue
-                flat_sr(cur, o)
-                sl = slice(o, o + n)
-                C.adamw_t_sr_(f.data[sl].view(rows, cols), f.grad[sl].view(rows, cols), m[sl].view(rows, cols),
-                              v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, *tail,
-                              **self._sr_kwargs(o))
-                cur = o + n
-            flat_sr(cur, hi)
-            if not FUSED_T:
-                f.refresh_transposed(lo, hi)
-            for o in rest:
-                f.refresh_transposed(o, o + 1)
-            return
         if self.master is not None:
             # fp32 master update, then the transposed shadows of the matrices in range from the
             # rounded parameters (same stream: the next backward sees them; sharded: after the gather)
-            C.adamw_master_(f.data[lo:hi], self.master[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, *tail)
+            C.adamw_master_(f.data[lo:hi], self.master[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args)
             if not sharded:
                 f.refresh_transposed(lo, hi)
             return
+        # stochastic rounding: the same launches through the SR entry points, every slice with its flat
+        # position, so the bits do not depend on how the range is cut
+        flat_fn, t_fn = (C.adamw_flat_sr_, C.adamw_t_sr_) if self.sr_mask else (C.adamw_flat_, C.adamw_t_)
+        sr = self._sr_kwargs if self.sr_mask else (lambda base: {})
+
+        def update_flat(a, b):
+            if a < b:
+                flat_fn(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, **sr(a))
+
+        def update_matrix(o, rows, cols):
+            sl = slice(o, o + rows * cols)
+            t_fn(f.data[sl].view(rows, cols), f.grad[sl].view(rows, cols), m[sl].view(rows, cols),
+                 v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, **sr(o))
+
         if sharded:
             # an owned chunk cuts matrices: plain update; the shadows are re-derived from the gathered
             # parameters (step)
-            C.adamw_flat_(f.data[lo:hi], f.grad[lo:hi], m[lo:hi], v[lo:hi], *args, *tail)
+            update_flat(lo, hi)
             return
-
-        def flat_update(a, b):
-            if a < b:
-                C.adamw_flat_(f.data[a:b], f.grad[a:b], m[a:b], v[a:b], *args, *tail)
-
-        mats = f.transposed_in(lo, hi) if FUSED_T else []
-        cur = lo
-        rest = []
-        for o, rows, cols in mats:
-            n = rows * cols
-            if o + n > hi:  # (buckets align to fusion groups; kept for safety)
+        cur, rest = lo, []
+        for o, rows, cols in (f.transposed_in(lo, hi) if FUSED_T else []):
+            if o + rows * cols > hi:  # (buckets align to fusion groups; kept for safety)
                 rest.append(o)
                 continue
-            flat_update(cur, o)
-            sl = slice(o, o + n)
-            C.adamw_t_(f.data[sl].view(rows, cols), f.grad[sl].view(rows, cols), m[sl].view(rows, cols),
-                       v[sl].view(rows, cols), f.data_t[sl].view(cols, rows), *args, *tail)
-            cur = o + n
-        flat_update(cur, hi)
+            update_flat(cur, o)
+            update_matrix(o, rows, cols)
+            cur = o + rows * cols
+        update_flat(cur, hi)
         if not FUSED_T:
             f.refresh_transposed(lo, hi)  # same stream: the next backward sees the new weights
+        # A matrix that hi cuts was updated up to hi by the flat launches above; its shadow is re-derived
+        # here from the whole matrix. That does not make the shadow right: the part beyond hi is updated by
+        # a later range, and that range (the matrix starts before its lo) does not refresh the shadow again.
         for o in rest:
             f.refresh_transposed(o, o + 1)
 
@@ -522,7 +500,6 @@ class FlatAdamW(torch.optim.AdamW):
             self._in_step = False
             self._done_ranges = []
             return loss
-        g = self.param_groups[0]
         if self.guard is not None:
             # the guard ran on this step's gradient (LossScaleGuard.run). GPU: skip flag, multiplier and
             # bias corrections are in device memory; CPU: the applied count is read here
@@ -533,11 +510,7 @@ class FlatAdamW(torch.optim.AdamW):
                 self._step = int(self.guard.state[LossScaleGuard.APPLIED])
         elif not self.graph_mode:
             self._step += 1
-        b1, b2 = g["betas"]
-        lr, eps, wd = float(g["lr"]), float(g["eps"]), float(g["weight_decay"])
-        bc1 = 1.0 - b1 ** self._step
-        bc2_sqrt = math.sqrt(1.0 - b2 ** self._step)
-        coeffs = (lr, b1, b2, eps, wd, bc1, bc2_sqrt)
+        coeffs = self._coeffs()
         r = getattr(self.flat, "reducer", None)
         if r is not None and r.shard:
             for b, (lo, hi) in enumerate(r.ranges):

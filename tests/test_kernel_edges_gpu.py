@@ -482,3 +482,51 @@ def test_adamw_on_slices_leaves_guards(cuda, kind, dtype, fast):
         assert torch.equal(big[off:off + n], a)
         assert torch.equal(big[:off], k[:off]) and torch.equal(big[off + n:], k[off + n:])
     assert not torch.equal(p[off:off + n], keep[0][off:off + n])
+
+
+def test_adamw_bindings_reject_bad_device_scalars(cuda):
+    """Each of the five AdamW entry points refuses every optional device scalar it takes (gscale_dev fp32[1],
+    hyper_dev fp64[3], skip_dev int32[1], and step_dev int32[1] for the stochastic-rounding ones) when it has
+    the wrong dtype, too few elements or lives on the host, before anything is launched: the state stays
+    bit-equal. The host tensor comes last in each group, after the harmless cases. A valid call with all of
+    them then updates p."""
+    C = _ext.native()
+    bf, i32 = torch.bfloat16, torch.int32
+    gen = torch.Generator(device=cuda).manual_seed(11)
+    # lr = 1: one step moves p by about 0.03, several bf16 ulps, also where p is the fp32 master rounded
+    co = (1.0, B1, B2, AEPS, WD, 1 - B1, math.sqrt(1 - B2), 1.0)
+    sr = dict(seed=1, base=0, step=1, mask=7)
+
+    def rnd(shape, dtype, scale=1.0):
+        return (torch.randn(shape, device=cuda, generator=gen) * scale).to(dtype)
+
+    def state(shape, sdt):  # p, g, m, v
+        return [rnd(shape, bf), rnd(shape, bf, 0.1), rnd(shape, sdt, 1e-3), rnd(shape, sdt, 1e-2).abs()]
+
+    flat, mat = state(64, bf), state((64, 64), bf)
+    p, g, m, v = state(64, F32)
+    master = [p, p.float(), g, m, v]  # p, pm, g, m, v
+    entries = [("flat", C.adamw_flat_, flat, {}), ("master", C.adamw_master_, master, {}),
+               ("t", C.adamw_t_, mat + [torch.zeros(64, 64, dtype=bf, device=cuda)], {}),
+               ("flat_sr", C.adamw_flat_sr_, [t.clone() for t in flat], sr),
+               ("t_sr", C.adamw_t_sr_, [t.clone() for t in mat] + [torch.zeros(64, 64, dtype=bf, device=cuda)], sr)]
+    # name: (valid values, dtype, a wrong dtype, too few elements)
+    scalars = {"gscale_dev": ([1.0], F32, torch.float64, 0), "hyper_dev": ([co[0], co[5], co[6]], torch.float64, F32, 2),
+               "skip_dev": ([0], i32, torch.int64, 0), "step_dev": ([1], i32, torch.int64, 0)}
+    for kind, fn, tensors, extra in entries:
+        keep = [t.clone() for t in tensors]
+        names = [k for k in scalars if k != "step_dev" or extra]
+        for name in names:
+            vals, dtype, wrong, few = scalars[name]
+            bad = [("dtype", torch.tensor(vals, dtype=wrong, device=cuda)),
+                   ("size", torch.tensor(vals[:few], dtype=dtype, device=cuda)),
+                   ("host", torch.tensor(vals, dtype=dtype))]
+            for what, t in bad:
+                with pytest.raises(RuntimeError):
+                    fn(*tensors, *co, **{**extra, name: t})
+                    pytest.fail(f"{kind}: {name} with a bad {what} was accepted")
+                for a, b in zip(tensors, keep):
+                    assert torch.equal(a, b), (kind, name, what)
+        good = {k: torch.tensor(scalars[k][0], dtype=scalars[k][1], device=cuda) for k in names}
+        fn(*tensors, *co, **{**extra, **good})
+        assert not torch.equal(tensors[0], keep[0]), kind
