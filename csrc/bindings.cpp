@@ -873,11 +873,14 @@ void check_attn_dtype(const at::Tensor& q) {
 // Non-causal attention passes the real length as the key bound `skv` (keys >= skv are masked).
 constexpr int64_t kSeqPad = 128;
 int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-at::Tensor pad_seq(const at::Tensor& t, int64_t Sp) {
+at::Tensor pad_seq(const at::Tensor& t, int64_t Sp) {  // t itself when it needs no padding
+  if (t.size(1) == Sp) return t;
   at::Tensor out = at::zeros({t.size(0), Sp, t.size(2), t.size(3)}, t.options());
   out.narrow(1, 0, t.size(1)).copy_(t);
   return out;
 }
+// tile: 64 for the plain forward (fp32: 128), 128 for the document-masked forward and every backward
+int64_t padded_len(int64_t S, int64_t tile) { return S % tile ? round_up(S, kSeqPad) : S; }
 
 // doc_start [B, S] int32 of a packed batch (attention_docs.hip): checked, and for a sequence that does not
 // tile, padded to Sp with the last document's start, so pad tokens continue the last document
@@ -893,10 +896,30 @@ void check_doc_start(const at::Tensor& q, const at::Tensor& ds, int64_t B, int64
 }
 at::Tensor pad_doc_start(const at::Tensor& ds, int64_t Sp) {
   const int64_t B = ds.size(0), S = ds.size(1);
+  if (S == Sp) return ds;
   at::Tensor out = at::empty({B, Sp}, ds.options());
   out.narrow(1, 0, S).copy_(ds);
   out.narrow(1, S, Sp - S).copy_(ds.narrow(1, S - 1, 1).expand({B, Sp - S}));
   return out;
+}
+
+// The forward's share of the argument block, from the (padded) tensors the kernels will see; skv is the
+// real sequence length.
+pra_attn_args attn_args(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+                        const at::Tensor& lse, const at::Tensor& doc_start, double scale, bool causal, int64_t skv) {
+  pra_attn_args a = {};
+  a.dtype = dt(q);
+  a.B = (int)q.size(0), a.S = (int)q.size(1), a.Hq = (int)q.size(2), a.Hkv = (int)k.size(2), a.D = (int)q.size(3);
+  a.skv = (int)skv;
+  a.causal = causal ? 1 : 0;
+  a.scale = (float)scale;
+  a.q = q.data_ptr(), a.ldq = q.stride(1);
+  a.k = k.data_ptr(), a.ldk = k.stride(1);
+  a.v = v.data_ptr(), a.ldv = v.stride(1);
+  a.o = o.data_ptr(), a.ldo = o.stride(1);
+  a.lse = lse.data_ptr<float>();
+  a.doc_start = doc_start.defined() ? doc_start.data_ptr<int>() : nullptr;
+  return a;
 }
 
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
@@ -914,39 +937,17 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
   TORCH_CHECK(Hq % Hkv == 0, "attention: n_heads must be a multiple of n_kv_heads");
   TORCH_CHECK(S > 0 && (S % 64 == 0 || S <= (int64_t)INT32_MAX - kSeqPad), "attention: bad seq_len");
   const c10::DeviceGuard guard(q.device());
-  if (doc_start.has_value()) {  // packed sequences: document-masked kernels (128-row blocks)
-    check_doc_start(q, *doc_start, B, S, causal);
-    const bool pad = S % kSeqPad != 0;
-    const int64_t Sp = round_up(S, kSeqPad);
-    at::Tensor qp = pad ? pad_seq(q, Sp) : q, kp = pad ? pad_seq(k, Sp) : k, vp = pad ? pad_seq(v, Sp) : v;
-    at::Tensor dsp = pad ? pad_doc_start(*doc_start, Sp) : *doc_start;
-    at::Tensor o = at::empty({B, Sp, Hq, D}, q.options());
-    at::Tensor lse = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
-    check(pra_attn_docs_fwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
-                            dsp.data_ptr<int>(), (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D, qp.stride(1),
-                            kp.stride(1), vp.stride(1), o.stride(1), (float)scale, stream_of(q)),
-          "attn_docs_fwd");
-    if (pad) return {o.narrow(1, 0, S).contiguous(), lse.narrow(2, 0, S).contiguous()};
-    return {o, lse};
-  }
-  const int64_t fwd_tile = q.scalar_type() == at::kFloat ? 128 : 64;  // fp32 kernel: 128-query blocks
-  if (S % fwd_tile) {
-    const int64_t Sp = round_up(S, kSeqPad);
-    at::Tensor qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp);
-    at::Tensor o = at::empty({B, Sp, Hq, D}, q.options());
-    at::Tensor lse = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
-    check(pra_attn_fwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
-                       (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D, qp.stride(1), kp.stride(1), vp.stride(1),
-                       o.stride(1), (float)scale, causal ? 1 : 0, (int)S, stream_of(q)),
-          "attn_fwd");
-    return {o.narrow(1, 0, S).contiguous(), lse.narrow(2, 0, S).contiguous()};
-  }
-  at::Tensor o = at::empty({B, S, Hq, D}, q.options());
-  at::Tensor lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  check(pra_attn_fwd(dt(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), (int)B,
-                     (int)S, (int)Hq, (int)Hkv, (int)D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
-                     (float)scale, causal ? 1 : 0, (int)S, stream_of(q)),
-        "attn_fwd");
+  const bool docs = doc_start.has_value();  // packed sequences: document-masked kernels (128-row blocks)
+  if (docs) check_doc_start(q, *doc_start, B, S, causal);
+  // fp32 kernel: 128-query blocks
+  const int64_t Sp = padded_len(S, docs || q.scalar_type() == at::kFloat ? kSeqPad : 64);
+  const at::Tensor qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp);
+  const at::Tensor dsp = docs ? pad_doc_start(*doc_start, Sp) : at::Tensor();
+  at::Tensor o = at::empty({B, Sp, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, Hq, Sp}, q.options().dtype(at::kFloat));
+  const pra_attn_args a = attn_args(qp, kp, vp, o, lse, dsp, scale, causal, S);
+  check(pra_attn_fwd(&a, stream_of(q)), docs ? "attn_docs_fwd" : "attn_fwd");
+  if (Sp != S) return {o.narrow(1, 0, S).contiguous(), lse.narrow(2, 0, S).contiguous()};
   return {o, lse};
 }
 
@@ -1037,14 +1038,10 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
   check_attn_dtype(q);
   const int64_t B = q.size(0), S = q.size(1), Hq = q.size(2), D = q.size(3), Hkv = k.size(2);
   const at::ScalarType ty = q.scalar_type();
-  check_bshd(q, "q", B, S, Hq, D, ty);
-  check_bshd(k, "k", B, S, Hkv, D, ty);
-  check_bshd(v, "v", B, S, Hkv, D, ty);
-  check_bshd(o, "o", B, S, Hq, D, ty);
-  check_bshd(dout, "dout", B, S, Hq, D, ty);
-  check_bshd(dq, "dq", B, S, Hq, D, ty);
-  check_bshd(dk, "dk", B, S, Hkv, D, ty);
-  check_bshd(dv, "dv", B, S, Hkv, D, ty);
+  const std::tuple<const at::Tensor&, const char*, int64_t> operands[] = {
+      {q, "q", Hq}, {k, "k", Hkv}, {v, "v", Hkv}, {o, "o", Hq}, {dout, "dout", Hq}, {dq, "dq", Hq}, {dk, "dk", Hkv},
+      {dv, "dv", Hkv}};
+  for (const auto& [t, name, H] : operands) check_bshd(t, name, B, S, H, D, ty);
   TORCH_CHECK(D == 64 || D == 128, "attention: head_dim must be 64 or 128");
   TORCH_CHECK(Hq % Hkv == 0, "attention: n_heads must be a multiple of n_kv_heads");
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == B * Hq * S && lse.is_contiguous(), "attention: lse");
@@ -1060,62 +1057,34 @@ void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, con
     rtab = tb.data_ptr<float>();
   }
   const c10::DeviceGuard guard(q.device());
-  if (doc_start.has_value()) {  // packed sequences: document-masked kernels
-    check_doc_start(q, *doc_start, B, S, causal);
-    const bool pad = S % kSeqPad != 0;
-    const int64_t Sp = round_up(S, kSeqPad);
-    at::Tensor qp = q, kp = k, vp = v, op = o, dop = dout, lp = lse, dqp = dq, dkp = dk, dvp = dv, dsp = *doc_start;
-    if (pad) {
-      qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp), op = pad_seq(o, Sp), dop = pad_seq(dout, Sp);
-      lp = at::zeros({B, Hq, Sp}, lse.options());  // padded rows: any finite lse (their dO is zero)
-      lp.narrow(2, 0, S).copy_(lse.view({B, Hq, S}));
-      dqp = at::empty_like(qp), dkp = at::empty_like(kp), dvp = at::empty_like(vp);
-      dsp = pad_doc_start(*doc_start, Sp);
-    }
-    at::Tensor ws = at::empty({pra_attn_docs_bwd_workspace((int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D)},
-                              q.options().dtype(at::kFloat));
-    check(pra_attn_docs_bwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(),
-                            lp.data_ptr<float>(), ws.data_ptr<float>(), dqp.data_ptr(), dkp.data_ptr(),
-                            dvp.data_ptr(), dsp.data_ptr<int>(), (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D,
-                            qp.stride(1), kp.stride(1), vp.stride(1), op.stride(1), dop.stride(1), dqp.stride(1),
-                            dkp.stride(1), dvp.stride(1), (float)scale, (int)S, rtab, mev, stream_of(q)),
-          "attn_docs_bwd");
-    if (pad) {
-      dq.copy_(dqp.narrow(1, 0, S));
-      dk.copy_(dkp.narrow(1, 0, S));
-      dv.copy_(dvp.narrow(1, 0, S));
-    }
-    return;
-  }
-  if (S % kSeqPad) {
-    const int64_t Sp = round_up(S, kSeqPad);
-    at::Tensor qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp), op = pad_seq(o, Sp),
-               dop = pad_seq(dout, Sp);
-    // padded rows: any finite lse (their dO is zero)
-    at::Tensor lp = at::zeros({B, Hq, Sp}, lse.options());
+  const bool docs = doc_start.has_value();  // packed sequences: document-masked kernels
+  if (docs) check_doc_start(q, *doc_start, B, S, causal);
+  const int64_t Sp = padded_len(S, kSeqPad);
+  const bool pad = Sp != S;
+  const at::Tensor qp = pad_seq(q, Sp), kp = pad_seq(k, Sp), vp = pad_seq(v, Sp), op = pad_seq(o, Sp),
+                   dop = pad_seq(dout, Sp);
+  const at::Tensor dsp = docs ? pad_doc_start(*doc_start, Sp) : at::Tensor();
+  at::Tensor lp = lse, dqp = dq, dkp = dk, dvp = dv;
+  if (pad) {
+    lp = at::zeros({B, Hq, Sp}, lse.options());  // padded rows: any finite lse (their dO is zero)
     lp.narrow(2, 0, S).copy_(lse.view({B, Hq, S}));
-    at::Tensor dqp = at::empty_like(qp), dkp = at::empty_like(kp), dvp = at::empty_like(vp);
-    at::Tensor delta = at::empty({pra_attn_bwd_workspace(dt(q), (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D)},
-                                 q.options().dtype(at::kFloat));
-    check(pra_attn_bwd(dt(q), qp.data_ptr(), kp.data_ptr(), vp.data_ptr(), op.data_ptr(), dop.data_ptr(),
-                       lp.data_ptr<float>(), delta.data_ptr<float>(), dqp.data_ptr(), dkp.data_ptr(), dvp.data_ptr(),
-                       (int)B, (int)Sp, (int)Hq, (int)Hkv, (int)D, qp.stride(1), kp.stride(1), vp.stride(1),
-                       op.stride(1), dop.stride(1), dqp.stride(1), dkp.stride(1), dvp.stride(1), (float)scale,
-                       causal ? 1 : 0, (int)S, rtab, mev, stream_of(q)),
-          "attn_bwd");
+    dqp = at::empty_like(qp), dkp = at::empty_like(kp), dvp = at::empty_like(vp);
+  }
+  pra_attn_args a = attn_args(qp, kp, vp, op, lp, dsp, scale, causal, S);
+  a.dout = dop.data_ptr(), a.lddo = dop.stride(1);
+  a.dq = dqp.data_ptr(), a.lddq = dqp.stride(1);
+  a.dk = dkp.data_ptr(), a.lddk = dkp.stride(1);
+  a.dv = dvp.data_ptr(), a.lddv = dvp.stride(1);
+  a.rope_tab = rtab;
+  a.mid_event = mev;
+  at::Tensor ws = at::empty({pra_attn_bwd_workspace(&a)}, q.options().dtype(at::kFloat));
+  a.ws = ws.data_ptr<float>();
+  check(pra_attn_bwd(&a, stream_of(q)), docs ? "attn_docs_bwd" : "attn_bwd");
+  if (pad) {
     dq.copy_(dqp.narrow(1, 0, S));
     dk.copy_(dkp.narrow(1, 0, S));
     dv.copy_(dvp.narrow(1, 0, S));
-    return;
   }
-  at::Tensor delta = at::empty({pra_attn_bwd_workspace(dt(q), (int)B, (int)S, (int)Hq, (int)Hkv, (int)D)},
-                               q.options().dtype(at::kFloat));
-  check(pra_attn_bwd(dt(q), q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
-                     lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                     (int)B, (int)S, (int)Hq, (int)Hkv, (int)D, q.stride(1), k.stride(1), v.stride(1), o.stride(1),
-                     dout.stride(1), dq.stride(1), dk.stride(1), dv.stride(1), (float)scale, causal ? 1 : 0, (int)S,
-                     rtab, mev, stream_of(q)),
-        "attn_bwd");
 }
 
 }  // namespace
@@ -1187,16 +1156,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"));
   m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
-  m.def("attn_set_order", [](int fwd, int dq, int dkdv) { pra_attn_set_order(fwd, dq, dkdv); },
-        "block order of the attention grids: 0 = heavy tiles first, G > 0 = XCD-grouped with G heads per group, "
-        "-1 = by shape", pybind11::arg("fwd"), pybind11::arg("dq"), pybind11::arg("dkdv"));
+  // every field of pra_attn_options (csrc/kernels/attn_plan.h documents them), by keyword
   m.def("attn_set_options", [](int fwd_pipe, double fwd_thr, int dkdv_impl, int dq_pipe, int dkdv_split, int dkdv_kreg,
-                               int bwd_fused, int bwd_window) {
-    pra_attn_set_options(fwd_pipe, (float)fwd_thr, dkdv_impl, dq_pipe, dkdv_split, dkdv_kreg, bwd_fused, bwd_window);
-  }, "attention kernel selection: fwd_pipe / dkdv_impl / dq_pipe = -1 (by shape), 0 or 1; fwd_thr = rescale "
-     "threshold (log2); dkdv_split = -1 (by grid) or query-head splits of the pipelined dK/dV kernel; "
-     "dkdv_kreg = 2: ring-staged dK/dV kernel, -2 (default): ring unless a side-stream job waits for the dK/dV window, 1: two-wave dK/dV kernel keeps K in registers, 0: K in LDS; "
-     "bwd_fused = -1 (by shape), 0 (split kernels) or 1: fused dQ/dK/dV kernel; bwd_window = 0: side-stream window between dQ and dK/dV, 1: before dQ");
+                               int bwd_fused, int bwd_window, int fwd_order, int dq_order, int dkdv_order) {
+    const pra_attn_options o = {fwd_pipe,  (float)fwd_thr, dkdv_impl, dq_pipe,  dkdv_split, dkdv_kreg,
+                                bwd_fused, bwd_window,     fwd_order, dq_order, dkdv_order};
+    pra_attn_set_options(&o);
+  }, py::kw_only(), py::arg("fwd_pipe"), py::arg("fwd_thr"), py::arg("dkdv_impl"), py::arg("dq_pipe"),
+     py::arg("dkdv_split"), py::arg("dkdv_kreg"), py::arg("bwd_fused"), py::arg("bwd_window"), py::arg("fwd_order"),
+     py::arg("dq_order"), py::arg("dkdv_order"));
   register_ckpt_engine(m);
   register_xgmi(m);
 }

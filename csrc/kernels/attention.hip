@@ -30,9 +30,7 @@
 // B1 S8192 H32/8 causal: bwd 2.68 -> 1.91 ms with the pipelined kernels (719 TF model, 1.0 PF executed).
 #include "attn_common.h"
 #include "common.h"
-#include "launchers.h"
-
-#include <type_traits>
+#include "attn_launch.h"
 
 // Variant switches (tools/attn_variants.sh builds the standalone harness per setting)
 #ifndef PRA_FWD_MINBLK
@@ -1327,152 +1325,8 @@ using namespace pra::attn;
 
 namespace {
 
-// Kernel selection knobs. Set through pra_attn_set_options (pyrecover_amd.ops.fused reads the
-// PYRECOVER_ATTN_* environment once; tests switch them per case); the launchers read no environment.
-struct AttnOptions {
-  // forward: -1 = by shape (pipelined fwd_p_kernel for causal, fwd_kernel for full attention),
-  // 0 = fwd_kernel, 1 = fwd_p_kernel (a 16x16x32 forward of fwd_kernel's structure measured 0.766 vs
-  // 0.727 ms for fwd_p_kernel, profiles/r5/attn/fwd16_vs_fwd.log, and was removed). The pipelined kernel's non-causal instantiation spills at
-  // D = 128, and padded non-causal keys (skv < S) need fwd_kernel's key bound.
-  // (B8 S2048 H32: 0.460 -> 0.422 ms; S8192 H32/8: 0.654 -> 0.615 ms with the pipelined kernel.)
-  int fwd_pipe = -1;
-  // Rescale threshold of the pipelined forward (cdna guide T13), log2 units: O and l are rescaled
-  // only when some row's max grows by more than thr, so P stays below 2^thr (fp32 accumulators;
-  // bf16 P keeps its relative precision). 0 = exact rescale at every growth.
-  float fwd_thr = 8.f;
-  // dK/dV: -1 = by shape (dkdv_use_p2), 0 = two-wave bwd_dkdv_kernel, 1 = pipelined bwd_dkdv_p2_kernel
-  int dkdv_impl = -1;
-  // dQ: -1/1 = region-pipelined bwd_dq_kernel<PIPE>, 0 = plain (padded non-causal keys: always plain)
-  int dq_pipe = -1;
-  // pipelined dK/dV kernel, query heads per block: 1 = all of the kv head's Hq / Hkv heads in one
-  // block (default), n = Hq / Hkv / n heads per block plus an fp32 reduction, -1 = by grid size
-  // (dkdv_split) when no side-stream job waits for the window. Not by default: it pays only without
-  // the overlapped optimizer, and its fp32 partial sums would make the gradients depend on whether
-  // the optimizer overlaps (tests/test_xgmi_gpu.py compares the two bitwise)
-  int dkdv_split = 1;
-  // two-wave dK/dV kernel (NW = 8, D = 128): 2 = ring-staged bwd_dkdv_r_kernel (K in registers,
-  // Q/dO by LDS-DMA, one barrier per query tile; B16 S2048 H32 bwd 2.39 -> 2.27 ms,
-  // profiles/r5/attn/harness_dkdv_ring.log), 1 = bwd_dkdv_kernel with K fragments held in registers
-  // (KREG), 0 = bwd_dkdv_kernel reading K from LDS, -1 = KREG unless a side-stream job waits for the
-  // dK/dV window (below) (r4: KREG 2.387 -> 2.358 ms alone, but 1058.0 vs 1055.5 ms in the 7B step:
-  // profiles/r4/attn_ab_dkdv_kreg_b16.log, step_ab_7b_b16_kreg.log), -2 (default) = the ring kernel
-  // unless a side-stream job waits for the window, else 0: the ring kernel's 242 VGPRs leave no
-  // room on the SIMDs for the overlapped AdamW waves (the LDS kernel's 215 do), so in the overlapped
-  // 7B B16 step it is not faster (1054.7 vs 1053.3 ms, profiles/r5/step_ab_ring.log)
-  int dkdv_kreg = -2;
-  // fused backward (attention_bwd_fused.hip: dQ, dK, dV in one workgroup per (batch, kv head)):
-  // -1 = by shape (attn_bwd_use_fused), 0 = never (split dQ + dK/dV kernels; the default), 1 = whenever
-  // it applies. Not the default: alone it is faster (7B B16 step without the AdamW update 1032.7 ->
-  // 1025.7 ms), but its 256-VGPR waves leave no room for the overlapped update's waves, which the split
-  // dK/dV kernel hosts (with the update 1045.4 vs 1048.3 ms; profiles/r5/attn_fused/). The choice must
-  // not depend on the window (dQ differs in the last bits), so it is a run-wide setting.
-  int bwd_fused = 0;
-  // where the side-stream window (mid_event) opens in the split backward: 0 = between the dQ and
-  // the dK/dV kernels, 1 = before the dQ kernel (the update then runs beside both), -1 (default) = by
-  // shape (window_before_dq): before dQ at <= 4096 tokens per call, where the dK/dV kernel alone is
-  // too short a window (same-process A/B: Llama-3-8B B1 S2048 110.06 -> 109.61 ms, 7B B1 98.62 ->
-  // 97.96 ms; at 8192 tokens slower: 8B S8192 B1 +2.35%, 8B S2048 B4 +0.33%, 7B B16 +0.5%;
-  // profiles/r5/window/). Bitwise neutral: only the event moves.
-  int bwd_window = -1;
-  // block order of the pipelined forward (block_tile): 0 = heavy query tiles first across the grid,
-  // G > 0 = XCD-grouped, G heads per group; -1 = by shape (attn_grp)
-  int fwd_order = 0;
-  int dq_order = 0;    // the same for the dQ kernel
-  int dkdv_order = 0;  // and the two-wave / ring dK/dV kernels (key tiles, lightest last)
-  // (A higher s_setprio for the backward kernels' waves than the overlapped AdamW update's, 1 or 3,
-  // dK/dV and dQ: neutral in the 7B B16 step, 1058.0 / 1058.2 vs 1058.0 ms; profiles/r6/
-  // step_ab_7b_b16_bwd_prio.log. Removed.)
-};
-AttnOptions g_attn_opts;
+pra_attn_options g_attn_opts;  // attn_plan.h
 
-static bool window_before_dq(int B, int S) {
-  const int w = g_attn_opts.bwd_window;
-  return w == 1 || (w < 0 && (long)B * S <= 4096);
-}
-
-// Heads per XCD group for an nqt x BH grid under option `order`, 0 when the grid does not split.
-// By shape (order < 0): at least the rep = Hq / Hkv query heads that share a kv head (forward and dQ
-// grids; 1 for the dK/dV grids, whose heads are kv heads), and at least 32 blocks (one per CU of
-// an XCD) per group. B16 S2048 H32 D128 causal (harness, profiles/r5/attn_order/): forward
-// 0.740 -> 0.650 ms, dQ + dK/dV 2.31 -> 2.11 ms; B1 S8192 H32/8 forward 0.508 -> 0.499 ms.
-static int attn_grp(int order, int nqt, int BH, int rep) {
-  if (order == 0 || BH % 8) return 0;
-  int g = order > 0 ? order : 1;
-  if (order < 0)
-    while ((g * 2 <= rep || g * 2 * nqt <= 32) && (BH / 8) % (g * 2) == 0) g *= 2;
-  return (BH / 8) % g == 0 ? g : 0;
-}
-
-// All tensors bf16 or fp16 (T), layout [B, S, H, D] with token stride ld* (elements); LSE/Delta fp32 [B, Hq, S].
-template <typename T>
-hipError_t attn_fwd_t(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
-                        int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int skv,
-                        hipStream_t st) {
-  if (S % 64 || (D != 64 && D != 128) || Hq % Hkv) return hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return hipErrorInvalidValue;
-  constexpr int NW = 8;
-  const int nqt = (S + 32 * NW - 1) / (32 * NW);
-  dim3 grid(nqt * Hq * B), block(NW * 64);
-  const float sl2 = scale * 1.4426950408889634f;
-  const AttnOptions& op = g_attn_opts;
-  const bool pipe = (causal || skv >= S) && (op.fwd_pipe >= 0 ? op.fwd_pipe != 0 : (causal != 0));
-  const float thr = op.fwd_thr;
-  const int grp = attn_grp(op.fwd_order, nqt, Hq * B, Hq / Hkv);
-#define LAUNCH(DD, CC)                                                                                        \
-  if (pipe)                                                                                                   \
-    hipLaunchKernelGGL((fwd_p_kernel<T, DD, CC, NW>), grid, block, 0, st, (const T*)q, (const T*)k,         \
-                       (const T*)v, (T*)o, lse, S, Hq, Hkv, ldq, ldk, ldv, ldo, sl2, thr, grp);             \
-  else                                                                                                        \
-    hipLaunchKernelGGL((fwd_kernel<T, DD, CC, NW>), grid, block, 0, st, (const T*)q, (const T*)k,           \
-                       (const T*)v, (T*)o, lse, S, Hq, Hkv, ldq, ldk, ldv, ldo, sl2, skv)
-  if (D == 128) { if (causal) LAUNCH(128, true); else LAUNCH(128, false); }
-  else { if (causal) LAUNCH(64, true); else LAUNCH(64, false); }
-#undef LAUNCH
-  return hipGetLastError();
-}
-
-// dK/dV kernel choice. D = 64: 64 KB of LDS and <= 256 VGPRs, so two pipelined one-wave blocks share
-// a CU and hide each other's prologue (B16 S2048 H16: 0.74 -> 0.68 ms bwd). At D = 128 the pipelined
-// kernel wins only while the two-wave kernel's grid ((S/256) Hkv B blocks, one per CU) is at most one
-// round of the chip's 256 CUs, where its causal work imbalance is exposed: S 8192 GQA 32/8 bwd B1
-// 2.56 -> 1.98 ms with p2, but B4 7.30 (two-wave) vs 7.89 ms (p2) (profiles/attn_dkdv_select_r2.log).
-static bool dkdv_use_p2(int B, int S, int Hq, int Hkv, int D) {
-  const int impl = g_attn_opts.dkdv_impl;
-  const long grid2 = (long)(S / 256) * Hkv * B;
-  return impl == 1 || (impl < 0 && (D == 64 || ((long)(Hq / Hkv) * S >= 8192 && grid2 <= 256)));
-}
-
-// Window rule (dkdv_split / dkdv_kreg = -1): when the caller hands a mid_event, a side-stream job
-// (the overlapped AdamW update, ops/sched.py) runs beside the dK/dV kernel, and a shorter kernel only
-// pushes the rest of that job onto the GEMMs after it. In the step, the faster variants then lose:
-// Llama-3-8B B1 S2048 109.1 ms split vs 108.3 unsplit (eager update: 109.7 vs 113.6), 7B B16
-// 1058.0 KREG vs 1055.5 (profiles/r4/step_ab_*_split_sched.log, *_kreg.log). So both apply only
-// when no job waits for the window (e.g. gradient-accumulation micro-steps, no overlapped update).
-//
-// GQA at small batch: the pipelined dK/dV grid is (S / 128) Hkv B blocks, one per CU at D = 128
-// (Llama-3-8B B1 S2048 bwd 0.297 -> 0.206 (2 splits) -> 0.172 ms (4); S8192: 1.717 ms unsplit, the
-// best: profiles/r4/attn_ab_dkdv_split_*.log)
-// -- 128 blocks (half the chip) for Llama-3-8B B1 S2048 H32/8, and the causal work per block falls
-// 16:1 from the first key block to the last. Splitting the kv head's query heads over n blocks gives
-// n times the grid; with the heavy key blocks dispatched first, a CU that drew a light block picks
-// up the next one, so two rounds of blocks even out to ~ (S/128 + 1) / 2 steps of work per CU. The
-// price is an fp32 partial per split and one reduction pass (2 n B S Hkv D floats).
-static int dkdv_split(int B, int S, int Hq, int Hkv, int D) {
-  const int nrep = Hq / Hkv;
-  int n = g_attn_opts.dkdv_split;
-  if (n < 0) {
-    const long grid = (long)(S / 128) * Hkv * B, want = D == 64 ? 1024 : 512;
-    n = 1;
-    while (grid * n < want && nrep % (2 * n) == 0) n *= 2;
-  }
-  return (n >= 1 && nrep % n == 0) ? n : 1;
-}
-
-// Fused backward (attention_bwd_fused.hip) applies at D = 128, S % 256 == 0 without key padding. By
-// shape it runs when its grid -- one workgroup per (batch, kv head), each walking all S / 256 key
-// blocks -- fills whole rounds of the chip (>= 90% of the slots of its last round busy): 7B-class MHA
-// at batch >= 8. Its choice never depends on the AdamW window (mid_event), so overlapped and plain
-// optimizer steps see the same gradients.
 static int device_cus() {
   static int cus[64] = {0};
   int d = 0;
@@ -1481,132 +1335,107 @@ static int device_cus() {
     cus[d] = 256;
   return cus[d];
 }
-static bool fused_shape_ok(int S, int D) { return D == 128 && S % 256 == 0; }
-static bool attn_bwd_use_fused(int B, int S, int Hq, int Hkv, int D, int skv) {
-  const int mode = g_attn_opts.bwd_fused;
-  if (mode == 0 || !fused_shape_ok(S, D) || skv != S) return false;
-  if (mode == 1) return true;
-  const long grid = (long)B * Hkv, cus = device_cus();
-  const long rounds = (grid + cus - 1) / cus;
-  return grid >= cus && grid * 10 >= rounds * cus * 9;
+
+// bf16 / fp16 family: S a multiple of `tile` (64 forward, 128 backward), head_dim 64 or 128
+bool shape_ok(const pra_attn_args& a, int tile, bool bwd) {
+  if (a.S % tile || (a.D != 64 && a.D != 128) || a.Hq % a.Hkv) return false;
+  return strides_ok(a, bwd, 8);
 }
 
-// fp32 workspace of pra_attn_bwd, in floats: delta, the row constants (-lse / scale, -delta) of the
-// pipelined dK/dV kernel and the fused kernel, the dK/dV split partials, or the fused kernel's dQ partials
-long attn_bwd_ws_floats(int B, int S, int Hq, int Hkv, int D) {
-  const long nrc = (long)B * Hq * S;
-  const bool p2 = dkdv_use_p2(B, S, Hq, Hkv, D);
-  const int n = p2 ? dkdv_split(B, S, Hq, Hkv, D) : 1;
-  const long split = 3 * nrc + (n > 1 ? 2L * n * B * S * Hkv * D : 0);
-  const long fused = g_attn_opts.bwd_fused != 0 && fused_shape_ok(S, D) ? 3 * nrc + nrc * D + 1024L * B * Hkv : 0;
-  return split > fused ? split : fused;
-}
-
+// All tensors bf16 or fp16 (T), layout [B, S, H, D] with token stride ld* (elements); LSE/Delta fp32 [B, Hq, S].
 template <typename T>
-hipError_t attn_bwd_t(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                        const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
-                        int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
-                        float scale, int causal, int skv, const float* rope_tab, hipEvent_t mid_event,
-                        hipStream_t st) {
-  if (S % 128 || (D != 64 && D != 128) || Hq % Hkv) return hipErrorInvalidValue;
-  const float2* rt = reinterpret_cast<const float2*>(rope_tab);
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 8 || lddk % 8 || lddv % 8)
-    return hipErrorInvalidValue;
-  if (attn_bwd_use_fused(B, S, Hq, Hkv, D, skv)) {
-    // the window (mid_event) opens after the memory-bound row-constant pass, beside the fused kernel
-    const long nrc = (long)B * Hq * S;
-    return pra_attn_bwd_fused(std::is_same<T, __bf16>::value ? pra::kBF16 : pra::kF16, q, k, v, o, dout, lse,
-                              delta + nrc, dq, dk, dv, B, S, Hq, Hkv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
-                              scale, causal, rope_tab, mid_event, st);
-  }
-  const float sl2 = scale * 1.4426950408889634f;
-  // 8-wave (256-row) blocks; S % 256 != 0 (S % 128 == 0) takes the 4-wave instantiations
-  const int nw = S % 256 ? 4 : 8;
-  // delta: fp32 workspace [3][B * Hq * S]: delta, then the pipelined dK/dV kernel's row constants
-  // (-lse / scale, -delta), written by the dQ kernel only when that kernel runs
+hipError_t attn_fwd_t(const pra_attn_args& a, hipStream_t st) {
+  constexpr int NW = 8;
+  const int nqt = (a.S + 32 * NW - 1) / (32 * NW);
+  const dim3 grid(nqt * a.Hq * a.B), block(NW * 64);
+  const float sl2 = a.scale * kLog2e;
+  const FwdPlan pl = fwd_plan(g_attn_opts, shape_of(a));
+  dispatch(
+      [&](auto d, auto c) {
+        if (pl.pipe)
+          hipLaunchKernelGGL((fwd_p_kernel<T, d(), c(), NW>), grid, block, 0, st, (const T*)a.q, (const T*)a.k,
+                             (const T*)a.v, (T*)a.o, a.lse, a.S, a.Hq, a.Hkv, a.ldq, a.ldk, a.ldv, a.ldo, sl2, pl.thr,
+                             pl.grp);
+        else
+          hipLaunchKernelGGL((fwd_kernel<T, d(), c(), NW>), grid, block, 0, st, (const T*)a.q, (const T*)a.k,
+                             (const T*)a.v, (T*)a.o, a.lse, a.S, a.Hq, a.Hkv, a.ldq, a.ldk, a.ldv, a.ldo, sl2, a.skv);
+      },
+      HeadDim{a.D}, Causal{a.causal != 0});
+  return hipGetLastError();
+}
+
+// Split backward: dQ first (it also computes delta = rowsum(dO * O), which the dK/dV kernel reads, and
+// the row constants when the plan's dK/dV kernel wants them), then the plan's dK/dV kernel.
+template <typename T>
+hipError_t attn_bwd_t(const pra_attn_args& a, const BwdPlan& pl, hipStream_t st) {
+  const T *q = (const T*)a.q, *k = (const T*)a.k, *v = (const T*)a.v, *dout = (const T*)a.dout;
+  T *dk = (T*)a.dk, *dv = (T*)a.dv;
+  const int B = a.B, S = a.S, Hq = a.Hq, Hkv = a.Hkv;
+  const float scale = a.scale, sl2 = scale * kLog2e;
+  const float2* rt = reinterpret_cast<const float2*>(a.rope_tab);
   const long nrc = (long)B * Hq * S;
-  const bool p2 = dkdv_use_p2(B, S, Hq, Hkv, D);
-  const bool ring = (g_attn_opts.dkdv_kreg == 2 || (g_attn_opts.dkdv_kreg == -2 && mid_event == nullptr)) && !p2 &&
-                    nw == 8 && D == 128;  // bwd_dkdv_r_kernel
-  float* rc2 = (p2 || ring) ? delta + nrc : nullptr;
-  // dQ first: it also computes delta = rowsum(dO * O), which the dK/dV kernel reads
-  const bool win_early = window_before_dq(B, S);
-  if (mid_event != nullptr && win_early) {
-    const hipError_t e = hipEventRecord(mid_event, st);
+  float* delta = a.ws + pl.delta;
+  float* rc2 = pl.rc >= 0 ? a.ws + pl.rc : nullptr;
+  const HeadDim d_{a.D};
+  const Causal c_{a.causal != 0};
+  const Waves nw_{pl.nw};
+  if (a.mid_event != nullptr && pl.win_early) {
+    const hipError_t e = hipEventRecord(a.mid_event, st);
     if (e != hipSuccess) return e;
   }
-  {
-    dim3 grid((S / (32 * nw)) * Hq * B);
-    // the pipelined kernel has no key bound: padded non-causal sequences take the plain one
-    const bool pipe = (causal || skv >= S) && g_attn_opts.dq_pipe != 0;
-    const int gq = attn_grp(g_attn_opts.dq_order, S / (32 * nw), Hq * B, Hq / Hkv);
-#define LAUNCH(DD, CC, NWW)                                                                                     \
-  if (pipe)                                                                                                     \
-    hipLaunchKernelGGL((bwd_dq_kernel<T, DD, CC, NWW, true>), grid, dim3(NWW * 64), 0, st, (const T*)q,       \
-                       (const T*)k, (const T*)v, (const T*)dout, (const T*)o, lse, delta, (T*)dq, S, Hq, Hkv,  \
-                       ldq, ldk, ldv, lddo, ldo, lddq, scale, sl2, skv, rt, rc2, nrc, gq);                          \
-  else                                                                                                          \
-    hipLaunchKernelGGL((bwd_dq_kernel<T, DD, CC, NWW>), grid, dim3(NWW * 64), 0, st, (const T*)q,             \
-                       (const T*)k, (const T*)v, (const T*)dout, (const T*)o, lse, delta, (T*)dq, S, Hq, Hkv,  \
-                       ldq, ldk, ldv, lddo, ldo, lddq, scale, sl2, skv, rt, rc2, nrc, gq)
-    if (nw == 8) {
-      if (D == 128) { if (causal) LAUNCH(128, true, 8); else LAUNCH(128, false, 8); }
-      else { if (causal) LAUNCH(64, true, 8); else LAUNCH(64, false, 8); }
-    } else {
-      if (D == 128) { if (causal) LAUNCH(128, true, 4); else LAUNCH(128, false, 4); }
-      else { if (causal) LAUNCH(64, true, 4); else LAUNCH(64, false, 4); }
-    }
-#undef LAUNCH
-  }
-  if (mid_event != nullptr && !win_early) {  // between dQ and dK/dV
-    const hipError_t e = hipEventRecord(mid_event, st);
+  dispatch(
+      [&](auto n, auto d, auto c) {
+        constexpr int NW = n();
+        auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, dim3((S / (32 * NW)) * Hq * B), dim3(NW * 64), 0, st, q, k, v, dout,
+                             (const T*)a.o, a.lse, delta, (T*)a.dq, S, Hq, Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.ldo,
+                             a.lddq, scale, sl2, a.skv, rt, rc2, nrc, pl.gq);
+        };
+        if (pl.dq_pipe) launch(bwd_dq_kernel<T, d(), c(), NW, true>);
+        else launch(bwd_dq_kernel<T, d(), c(), NW>);
+      },
+      nw_, d_, c_);
+  if (a.mid_event != nullptr && !pl.win_early) {  // between dQ and dK/dV
+    const hipError_t e = hipEventRecord(a.mid_event, st);
     if (e != hipSuccess) return e;
   }
-  const bool window = mid_event != nullptr;
-  if (p2) {
-    const int ns = window && g_attn_opts.dkdv_split < 0 ? 1 : dkdv_split(B, S, Hq, Hkv, D);
-    float* part = ns > 1 ? delta + 3 * nrc : nullptr;  // attn_bwd_ws_floats
-    dim3 g1((S / 128) * Hkv * B * ns);
-#define LAUNCH1(DD, CC)                                                                                       \
-  hipLaunchKernelGGL((bwd_dkdv_p2_kernel<T, DD, CC>), g1, dim3(256), 0, st, (const T*)q, (const T*)k,        \
-                     (const T*)v, (const T*)dout, rc2, rc2 + nrc, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv,   \
-                     lddo, lddk, lddv, scale, sl2, skv, rt, ns, part)
-    if (D == 128) { if (causal) LAUNCH1(128, true); else LAUNCH1(128, false); }
-    else { if (causal) LAUNCH1(64, true); else LAUNCH1(64, false); }
-#undef LAUNCH1
-    if (ns > 1) {
-      const long n = (long)B * S * Hkv * D;
+  if (pl.dkdv == kDkdvP2) {
+    float* part = pl.part >= 0 ? a.ws + pl.part : nullptr;
+    const dim3 g1((S / 128) * Hkv * B * pl.nsplit);
+    dispatch(
+        [&](auto d, auto c) {
+          hipLaunchKernelGGL((bwd_dkdv_p2_kernel<T, d(), c()>), g1, dim3(256), 0,
+                             st, q, k, v, dout, rc2, rc2 + nrc, dk, dv, S, Hq, Hkv, a.ldq, a.ldk, a.ldv, a.lddo,
+                             a.lddk, a.lddv, scale, sl2, a.skv, rt, pl.nsplit, part);
+        },
+        d_, c_);
+    if (pl.nsplit > 1) {
+      const long n = (long)B * S * Hkv * a.D;
       hipLaunchKernelGGL((dkdv_reduce_kernel<T>), dim3((unsigned)((2 * n / 4 + 255) / 256)), dim3(256), 0, st,
-                         (const float*)part, ns, n, Hkv * D, (T*)dk, lddk, (T*)dv, lddv);
+                         (const float*)part, pl.nsplit, n, Hkv * a.D, dk, a.lddk, dv, a.lddv);
     }
-  } else if (ring) {
-    dim3 grid((S / 256) * Hkv * B);
-#define LAUNCHR(DD, CC)                                                                                       \
-  hipLaunchKernelGGL((bwd_dkdv_r_kernel<T, DD, CC>), grid, dim3(512), 0, st, (const T*)q, (const T*)k,        \
-                     (const T*)v, (const T*)dout, rc2, nrc, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, lddo,   \
-                     lddk, lddv, scale, sl2, skv, rt, gk)
-    const int gk = attn_grp(g_attn_opts.dkdv_order, S / 256, Hkv * B, 1);
-    if (causal) LAUNCHR(128, true); else LAUNCHR(128, false);
-#undef LAUNCHR
+  } else if (pl.dkdv == kDkdvRing) {  // D = 128, nw = 8 (the plan chooses it nowhere else)
+    dispatch(
+        [&](auto c) {
+          hipLaunchKernelGGL((bwd_dkdv_r_kernel<T, 128, c()>), dim3((S / 256) * Hkv * B),
+                             dim3(512), 0, st, q, k, v, dout, rc2, nrc, dk, dv, S, Hq, Hkv, a.ldq, a.ldk, a.ldv,
+                             a.lddo, a.lddk, a.lddv, scale, sl2, a.skv, rt, pl.gk);
+        },
+        c_);
   } else {
-    dim3 grid((S / (32 * nw)) * Hkv * B);
-#define LAUNCH(DD, CC, NWW, ...)                                                                                \
-  hipLaunchKernelGGL((bwd_dkdv_kernel<T, DD, CC, NWW, ##__VA_ARGS__>), grid, dim3(NWW * 64), 0, st, (const T*)q,   \
-                     (const T*)k,                                                                               \
-                     (const T*)v, (const T*)dout, lse, delta, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, lddo,  \
-                     lddk, lddv, scale, sl2, skv, rt, gk)
-    const int gk = attn_grp(g_attn_opts.dkdv_order, S / (32 * nw), Hkv * B, 1);
-    const bool kreg = g_attn_opts.dkdv_kreg == 1 || (g_attn_opts.dkdv_kreg < 0 && !window);
-    if (nw == 8 && D == 128 && kreg) {
-      if (causal) LAUNCH(128, true, 8, true); else LAUNCH(128, false, 8, true);
-    } else if (nw == 8) {
-      if (D == 128) { if (causal) LAUNCH(128, true, 8); else LAUNCH(128, false, 8); }
-      else { if (causal) LAUNCH(64, true, 8); else LAUNCH(64, false, 8); }
-    } else {
-      if (D == 128) { if (causal) LAUNCH(128, true, 4); else LAUNCH(128, false, 4); }
-      else { if (causal) LAUNCH(64, true, 4); else LAUNCH(64, false, 4); }
-    }
-#undef LAUNCH
+    auto launch = [&](auto kernel, int nw) {
+      hipLaunchKernelGGL(kernel, dim3((S / (32 * nw)) * Hkv * B), dim3(nw * 64), 0, st, q, k, v, dout, a.lse, delta,
+                         dk, dv, S, Hq, Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.lddk, a.lddv, scale, sl2, a.skv, rt, pl.gk);
+    };
+    if (pl.dkdv == kDkdvKreg)  // instantiated, and chosen by the plan, at D = 128, nw = 8 only
+      dispatch([&](auto c) { launch(bwd_dkdv_kernel<T, 128, c(), 8, true>, 8); }, c_);
+    else
+      dispatch(
+          [&](auto n, auto d, auto c) {
+            constexpr int NW = n();
+            launch(bwd_dkdv_kernel<T, d(), c(), NW>, NW);
+          },
+          nw_, d_, c_);
   }
   return hipGetLastError();
 }
@@ -1615,67 +1444,34 @@ hipError_t attn_bwd_t(const void* q, const void* k, const void* v, const void* o
 
 extern "C" {
 
-hipError_t pra_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S,
-                        int Hq, int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal,
-                        int skv, hipStream_t st) {
-  if (skv <= 0 || skv > S) return hipErrorInvalidValue;
-  if (dtype == pra::kF32)
-    return pra_attn_fwd_f32((const float*)q, (const float*)k, (const float*)v, (float*)o, lse, B, S, Hq, Hkv, D, ldq,
-                            ldk, ldv, ldo, scale, causal, skv, st);
-  if (dtype == pra::kBF16)
-    return attn_fwd_t<__bf16>(q, k, v, o, lse, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, scale, causal, skv, st);
-#if !PRA_ATTN_HARNESS
-  if (dtype == pra::kF16)
-    return attn_fwd_t<_Float16>(q, k, v, o, lse, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, scale, causal, skv, st);
-#endif
-  return hipErrorInvalidValue;
+hipError_t pra_attn_fwd(const pra_attn_args* args, hipStream_t st) {
+  const pra_attn_args a = *args;
+  if (a.doc_start != nullptr) return docs_fwd(a, st);  // no key bound: skv is not read
+  if (a.skv <= 0 || a.skv > a.S) return hipErrorInvalidValue;
+  if (a.dtype == pra::kF32) return f32_fwd(a, st);
+  if (!shape_ok(a, 64, false)) return hipErrorInvalidValue;
+  return dispatch_16bit(a.dtype, [&](auto t) { return attn_fwd_t<decltype(t)>(a, st); });
 }
 
-hipError_t pra_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                        const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
-                        int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
-                        float scale, int causal, int skv, const float* rope_tab, hipEvent_t mid_event,
-                        hipStream_t st) {
-  if (skv <= 0 || skv > S) return hipErrorInvalidValue;
-  if (dtype == pra::kF32) {
-    if (rope_tab != nullptr) return hipErrorInvalidValue;  // the fp32 kernels have no fused inverse RoPE
-    return pra_attn_bwd_f32((const float*)q, (const float*)k, (const float*)v, (const float*)o, (const float*)dout,
-                            lse, delta, (float*)dq, (float*)dk, (float*)dv, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, lddo,
-                            lddq, lddk, lddv, scale, causal, skv, st);
-  }
-  if (dtype == pra::kBF16)
-    return attn_bwd_t<__bf16>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, lddo,
-                              lddq, lddk, lddv, scale, causal, skv, rope_tab, mid_event, st);
-#if !PRA_ATTN_HARNESS
-  if (dtype == pra::kF16)
-    return attn_bwd_t<_Float16>(q, k, v, o, dout, lse, delta, dq, dk, dv, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, lddo,
-                                lddq, lddk, lddv, scale, causal, skv, rope_tab, mid_event, st);
-#endif
-  return hipErrorInvalidValue;
+hipError_t pra_attn_bwd(const pra_attn_args* args, hipStream_t st) {
+  const pra_attn_args a = *args;
+  const BwdPlan pl = bwd_plan(g_attn_opts, shape_of(a), a.mid_event != nullptr, device_cus());
+  if (a.doc_start != nullptr) return docs_bwd(a, pl, st);
+  if (a.skv <= 0 || a.skv > a.S) return hipErrorInvalidValue;
+  // The fp32 backward never records mid_event: the event keeps the record its owner made before the
+  // call (ops/sched.py), so a side-stream job's window opens before this backward.
+  if (a.dtype == pra::kF32) return f32_bwd(a, st);
+  if (!shape_ok(a, 128, true)) return hipErrorInvalidValue;
+  // fused: the window (mid_event) opens after the memory-bound row-constant pass, beside the fused kernel
+  if (pl.fused) return fused_bwd(a, pl, st);
+  return dispatch_16bit(a.dtype, [&](auto t) { return attn_bwd_t<decltype(t)>(a, pl, st); });
 }
 
-// Kernel selection (see AttnOptions); not thread-safe against concurrent launches (set between steps).
-void pra_attn_set_options(int fwd_pipe, float fwd_thr, int dkdv_impl, int dq_pipe, int dkdv_split, int dkdv_kreg,
-                          int bwd_fused, int bwd_window) {
-  g_attn_opts.bwd_fused = bwd_fused;
-  g_attn_opts.bwd_window = bwd_window;
-  g_attn_opts.fwd_pipe = fwd_pipe;
-  g_attn_opts.fwd_thr = fwd_thr;
-  g_attn_opts.dkdv_impl = dkdv_impl;
-  g_attn_opts.dq_pipe = dq_pipe;
-  g_attn_opts.dkdv_split = dkdv_split;
-  g_attn_opts.dkdv_kreg = dkdv_kreg;
+long pra_attn_bwd_workspace(const pra_attn_args* a) {
+  return bwd_plan(g_attn_opts, shape_of(*a), a->mid_event != nullptr, device_cus()).ws_floats;
 }
 
-void pra_attn_set_order(int fwd, int dq, int dkdv) {
-  g_attn_opts.fwd_order = fwd;
-  g_attn_opts.dq_order = dq;
-  g_attn_opts.dkdv_order = dkdv;
-}
-
-long pra_attn_bwd_workspace(int dtype, int B, int S, int Hq, int Hkv, int D) {
-  if (dtype == pra::kF32) return 3L * B * Hq * S;
-  return attn_bwd_ws_floats(B, S, Hq, Hkv, D);
-}
+void pra_attn_get_options(pra_attn_options* out) { *out = g_attn_opts; }
+void pra_attn_set_options(const pra_attn_options* in) { g_attn_opts = *in; }
 
 }  // extern "C"

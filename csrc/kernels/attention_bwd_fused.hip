@@ -29,7 +29,7 @@
 // Replaces the reference's SDPA backward (reference model.py:179-230).
 #include "attn_common.h"
 #include "common.h"
-#include "launchers.h"
+#include "attn_launch.h"
 
 namespace pra {
 namespace attn {
@@ -292,52 +292,36 @@ __global__ __launch_bounds__(512, 1) PRA_FUSED_VGPR_ATTR void bwd_fused_kernel(
   }
 }
 
-}  // namespace attn
-}  // namespace pra
-
-extern "C" {
-
-// Host-checked preconditions (pra_attn_bwd_fused_ok): D = 128, S % 256 == 0, Hq % Hkv == 0, strides % 8.
-// ws: 2 B Hq S floats of row constants, then B Hq S D floats of dQ partials, then B Hkv 1024 floats of
-// per-workgroup scratch.
-hipError_t pra_attn_bwd_fused(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                              const float* lse, float* ws, void* dq, void* dk, void* dv, int B, int S, int Hq,
-                              int Hkv, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
-                              long lddv, float scale, int causal, const float* rope_tab, hipEvent_t mid_event,
-                              hipStream_t st) {
-  using namespace pra::attn;
-  if (S % 256 || S <= 0 || Hq % Hkv || B <= 0) return hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 8 || lddk % 8 || lddv % 8)
-    return hipErrorInvalidValue;
-  const long nrc = (long)B * Hq * S;
-  float* rc = ws;
-  float* acc = ws + 2 * nrc;
-  const float sl2 = scale * 1.4426950408889634f;
-  const float2* rt = reinterpret_cast<const float2*>(rope_tab);
-  const dim3 g0((unsigned)((nrc * 16 + 255) / 256)), g1((unsigned)(B * Hkv));
-#define PRA_FUSED(TT)                                                                                          \
-  hipLaunchKernelGGL((bwd_rowc_kernel<TT>), g0, dim3(256), 0, st, (const TT*)o, (const TT*)dout, lse, rc, nrc, S, \
-                     Hq, ldo, lddo, scale);                                                                    \
-  if (mid_event != nullptr && hipEventRecord(mid_event, st) != hipSuccess) return hipErrorInvalidResourceHandle; \
-  if (causal)                                                                                                  \
-    hipLaunchKernelGGL((bwd_fused_kernel<TT, true>), g1, dim3(512), 0, st, (const TT*)q, (const TT*)k,         \
-                       (const TT*)v, (const TT*)dout, rc, nrc, (TT*)dq, (TT*)dk, (TT*)dv, acc, S, Hq, Hkv, ldq,  \
-                       ldk, ldv, lddo, lddq, lddk, lddv, scale, sl2, rt);                                      \
-  else                                                                                                         \
-    hipLaunchKernelGGL((bwd_fused_kernel<TT, false>), g1, dim3(512), 0, st, (const TT*)q, (const TT*)k,        \
-                       (const TT*)v, (const TT*)dout, rc, nrc, (TT*)dq, (TT*)dk, (TT*)dv, acc, S, Hq, Hkv, ldq,  \
-                       ldk, ldv, lddo, lddq, lddk, lddv, scale, sl2, rt)
-  if (dtype == pra::kBF16) {
-    PRA_FUSED(__bf16);
-#if !PRA_ATTN_HARNESS
-  } else if (dtype == pra::kF16) {
-    PRA_FUSED(_Float16);
-#endif
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef PRA_FUSED
-  return hipGetLastError();
+// Preconditions beyond pra_attn_bwd's (the plan chooses this path at D = 128 only): S % 256 == 0 and
+// B, S > 0. Workspace (BwdPlan): rc = 2 B Hq S floats of row constants, acc = B Hq S D floats of dQ
+// partials, then B Hkv 1024 floats of per-workgroup scratch.
+hipError_t fused_bwd(const pra_attn_args& a, const BwdPlan& pl, hipStream_t st) {
+  if (a.S % 256 || a.S <= 0 || a.Hq % a.Hkv || a.B <= 0 || !strides_ok(a, true, 8)) return hipErrorInvalidValue;
+  const long nrc = (long)a.B * a.Hq * a.S;
+  float* rc = a.ws + pl.rc;
+  float* acc = a.ws + pl.acc;
+  const float sl2 = a.scale * kLog2e;
+  const float2* rt = reinterpret_cast<const float2*>(a.rope_tab);
+  const dim3 g0((unsigned)((nrc * 16 + 255) / 256)), g1((unsigned)(a.B * a.Hkv));
+  return dispatch_16bit(a.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((bwd_rowc_kernel<T>), g0, dim3(256), 0, st, (const T*)a.o, (const T*)a.dout, a.lse, rc, nrc,
+                       a.S, a.Hq, a.ldo, a.lddo, a.scale);
+    if (a.mid_event != nullptr) {
+      const hipError_t e = hipEventRecord(a.mid_event, st);
+      if (e != hipSuccess) return e;
+    }
+    dispatch(
+        [&](auto c) {
+          hipLaunchKernelGGL((bwd_fused_kernel<T, c()>), g1, dim3(512), 0, st, (const T*)a.q,
+                             (const T*)a.k, (const T*)a.v, (const T*)a.dout, rc, nrc, (T*)a.dq, (T*)a.dk, (T*)a.dv,
+                             acc, a.S, a.Hq, a.Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.lddq, a.lddk, a.lddv, a.scale, sl2,
+                             rt);
+        },
+        Causal{a.causal != 0});
+    return hipGetLastError();
+  });
 }
 
-}  // extern "C"
+}  // namespace attn
+}  // namespace pra

@@ -22,14 +22,11 @@
 // masks p with a select.
 #include "attn_common.h"
 #include "common.h"
-#include "launchers.h"
-
-#include <type_traits>
+#include "attn_launch.h"
 
 namespace pra {
 namespace attn {
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kNoMax = -1e30f;  // "no score yet" running max (log2 units; real scores are far above)
 
 __device__ __forceinline__ int doc_clamp(int ds, int i) { return min(max(ds, 0), i); }
@@ -474,106 +471,69 @@ __global__ __launch_bounds__(256, 2) void docs_bwd_dkdv_kernel(
   store_rows16<T, NDB>(dvt, 1.f, dV + ((long)b * S + krow) * lddv + hk * D, true, h2);
 }
 
-}  // namespace attn
-}  // namespace pra
-
-using namespace pra::attn;
-
 namespace {
 
-bool docs_shape_ok(int B, int S, int Hq, int Hkv, int D) {
-  return B > 0 && S > 0 && S % 128 == 0 && (D == 64 || D == 128) && Hkv > 0 && Hq % Hkv == 0 &&
-         (long)B * Hq * (S / 128) <= 0x7fffffffL;
-}
-
-template <typename T>
-hipError_t docs_fwd_t(const void* q, const void* k, const void* v, void* o, float* lse, const int* ds, int B, int S,
-                      int Hq, int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, hipStream_t st) {
-  dim3 grid((S / 128) * Hq * B), block(256);
-  const float sl2 = scale * kLog2e;
-#define LAUNCH(DD)                                                                                             \
-  hipLaunchKernelGGL((docs_fwd_kernel<T, DD>), grid, block, 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)o, \
-                     lse, ds, S, Hq, Hkv, ldq, ldk, ldv, ldo, sl2)
-  if (D == 128) LAUNCH(128); else LAUNCH(64);
-#undef LAUNCH
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t docs_bwd_t(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
-                      float* ws, void* dq, void* dk, void* dv, const int* ds, int B, int S, int Hq, int Hkv, int D,
-                      long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv, float scale,
-                      int skv, const float* rope_tab, hipEvent_t mid_event, hipStream_t st) {
-  const float2* rt = reinterpret_cast<const float2*>(rope_tab);
-  const float sl2 = scale * kLog2e;
-  float* delta = ws;                                                    // [B * Hq * S]
-  int* qend = reinterpret_cast<int*>(ws + (long)B * Hq * S);            // [B * S / 128]
-  hipLaunchKernelGGL(docs_qend_kernel, dim3(B * (S / 128)), dim3(256), 0, st, ds, qend, S);
-  {
-    dim3 grid((S / 128) * Hq * B);
-#define LAUNCH(DD)                                                                                              \
-  hipLaunchKernelGGL((docs_bwd_dq_kernel<T, DD>), grid, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, \
-                     (const T*)dout, (const T*)o, lse, delta, (T*)dq, ds, S, Hq, Hkv, ldq, ldk, ldv, lddo, ldo,  \
-                     lddq, scale, sl2, skv, rt)
-    if (D == 128) LAUNCH(128); else LAUNCH(64);
-#undef LAUNCH
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (mid_event != nullptr) {  // the side-stream window opens between dQ and dK/dV
-    e = hipEventRecord(mid_event, st);
-    if (e != hipSuccess) return e;
-  }
-  {
-    dim3 grid((S / 128) * Hkv * B);
-#define LAUNCH(DD)                                                                                                \
-  hipLaunchKernelGGL((docs_bwd_dkdv_kernel<T, DD>), grid, dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, \
-                     (const T*)dout, lse, (const float*)delta, (T*)dk, (T*)dv, ds, (const int*)qend, S, Hq, Hkv,   \
-                     ldq, ldk, ldv, lddo, lddk, lddv, scale, sl2, skv, rt)
-    if (D == 128) LAUNCH(128); else LAUNCH(64);
-#undef LAUNCH
-  }
-  return hipGetLastError();
+// the only family that bounds its grid and rejects B, Hkv <= 0
+bool docs_shape_ok(const pra_attn_args& a, bool bwd) {
+  return a.B > 0 && a.S > 0 && a.S % 128 == 0 && (a.D == 64 || a.D == 128) && a.Hkv > 0 && a.Hq % a.Hkv == 0 &&
+         (long)a.B * a.Hq * (a.S / 128) <= 0x7fffffffL && a.doc_start != nullptr && strides_ok(a, bwd, 8);
 }
 
 }  // namespace
 
-extern "C" {
-
-hipError_t pra_attn_docs_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
-                             const int* doc_start, int B, int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv,
-                             long ldo, float scale, hipStream_t st) {
-  if (!docs_shape_ok(B, S, Hq, Hkv, D) || doc_start == nullptr) return hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8) return hipErrorInvalidValue;
-  if (dtype == pra::kBF16)
-    return docs_fwd_t<__bf16>(q, k, v, o, lse, doc_start, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, scale, st);
-  if (dtype == pra::kF16)
-    return docs_fwd_t<_Float16>(q, k, v, o, lse, doc_start, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo, scale, st);
-  return hipErrorInvalidValue;
+hipError_t docs_fwd(const pra_attn_args& a, hipStream_t st) {
+  if (!docs_shape_ok(a, false)) return hipErrorInvalidValue;
+  const dim3 grid((a.S / 128) * a.Hq * a.B), block(256);
+  const float sl2 = a.scale * kLog2e;
+  return dispatch_16bit(a.dtype, [&](auto t) {
+    using T = decltype(t);
+    dispatch(
+        [&](auto d) {
+          hipLaunchKernelGGL((docs_fwd_kernel<T, d()>), grid, block, 0, st, (const T*)a.q,
+                             (const T*)a.k, (const T*)a.v, (T*)a.o, a.lse, a.doc_start, a.S, a.Hq, a.Hkv, a.ldq, a.ldk,
+                             a.ldv, a.ldo, sl2);
+        },
+        HeadDim{a.D});
+    return hipGetLastError();
+  });
 }
 
-hipError_t pra_attn_docs_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                             const float* lse, float* ws, void* dq, void* dk, void* dv, const int* doc_start, int B,
-                             int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo,
-                             long lddq, long lddk, long lddv, float scale, int skv, const float* rope_tab,
-                             hipEvent_t mid_event, hipStream_t st) {
-  if (!docs_shape_ok(B, S, Hq, Hkv, D) || doc_start == nullptr || skv <= 0 || skv > S) return hipErrorInvalidValue;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 8 || lddo % 8 || lddq % 8 || lddk % 8 || lddv % 8)
-    return hipErrorInvalidValue;
-  if (dtype == pra::kBF16)
-    return docs_bwd_t<__bf16>(q, k, v, o, dout, lse, ws, dq, dk, dv, doc_start, B, S, Hq, Hkv, D, ldq, ldk, ldv, ldo,
-                              lddo, lddq, lddk, lddv, scale, skv, rope_tab, mid_event, st);
-  if (dtype == pra::kF16)
-    return docs_bwd_t<_Float16>(q, k, v, o, dout, lse, ws, dq, dk, dv, doc_start, B, S, Hq, Hkv, D, ldq, ldk, ldv,
-                                ldo, lddo, lddq, lddk, lddv, scale, skv, rope_tab, mid_event, st);
-  return hipErrorInvalidValue;
+hipError_t docs_bwd(const pra_attn_args& a, const BwdPlan& pl, hipStream_t st) {
+  if (!docs_shape_ok(a, true) || a.skv <= 0 || a.skv > a.S) return hipErrorInvalidValue;
+  const int B = a.B, S = a.S, Hq = a.Hq, Hkv = a.Hkv;
+  const float2* rt = reinterpret_cast<const float2*>(a.rope_tab);
+  const float scale = a.scale, sl2 = scale * kLog2e;
+  const int* ds = a.doc_start;
+  float* delta = a.ws + pl.delta;
+  int* qend = reinterpret_cast<int*>(a.ws + pl.qend);
+  const HeadDim d_{a.D};
+  return dispatch_16bit(a.dtype, [&](auto t) {
+    using T = decltype(t);
+    const T *q = (const T*)a.q, *k = (const T*)a.k, *v = (const T*)a.v, *dout = (const T*)a.dout;
+    hipLaunchKernelGGL(docs_qend_kernel, dim3(B * (S / 128)), dim3(256), 0, st, ds, qend, S);
+    dispatch(
+        [&](auto d) {
+          hipLaunchKernelGGL((docs_bwd_dq_kernel<T, d()>), dim3((S / 128) * Hq * B), dim3(256), 0, st,
+                             q, k, v, dout, (const T*)a.o, a.lse, delta, (T*)a.dq, ds, S, Hq, Hkv, a.ldq, a.ldk, a.ldv,
+                             a.lddo, a.ldo, a.lddq, scale, sl2, a.skv, rt);
+        },
+        d_);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (a.mid_event != nullptr) {  // the side-stream window opens between dQ and dK/dV
+      e = hipEventRecord(a.mid_event, st);
+      if (e != hipSuccess) return e;
+    }
+    dispatch(
+        [&](auto d) {
+          hipLaunchKernelGGL((docs_bwd_dkdv_kernel<T, d()>), dim3((S / 128) * Hkv * B), dim3(256), 0,
+                             st, q, k, v, dout, a.lse, (const float*)delta, (T*)a.dk, (T*)a.dv, ds, (const int*)qend,
+                             S, Hq, Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.lddk, a.lddv, scale, sl2, a.skv, rt);
+        },
+        d_);
+    return hipGetLastError();
+  });
 }
 
-// fp32 words at `ws`: delta [B Hq S], then the dK/dV query-loop ends (int32) [B S / 128]
-long pra_attn_docs_bwd_workspace(int B, int S, int Hq, int Hkv, int D) {
-  (void)Hkv;
-  (void)D;
-  return (long)B * Hq * S + (long)B * (S / 128);
-}
-
-}  // extern "C"
+}  // namespace attn
+}  // namespace pra

@@ -23,6 +23,7 @@
 //  * dK/dV: 4 waves x 32 keys, each wave's K/V rows in registers (one wave per SIMD, 512-register
 //          file); loops over the query heads of its kv head and 32-query Q/dO tiles in LDS.
 // Determinism: no atomics; every output element has one writer and a fixed summation order.
+#include "attn_launch.h"
 #include "common.h"
 
 namespace pra {
@@ -304,55 +305,55 @@ __global__ __launch_bounds__(256, 1) void bwd_dkdv_kernel(
 }
 
 }  // namespace attnf
-}  // namespace pra
 
-extern "C" {
+namespace attn {
 
 // fp32 tensors [B, S, H, D] (token stride ld*); S % 128 == 0 (the binding zero-pads), D 64 or 128.
-hipError_t pra_attn_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int B, int S, int Hq,
-                            int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int skv,
-                            hipStream_t st) {
-  using namespace pra::attnf;
-  if (S % 128 || (D != 64 && D != 128) || Hq % Hkv || skv <= 0 || skv > S) return hipErrorInvalidValue;
-  if (ldq % 4 || ldk % 4 || ldv % 4 || ldo % 4) return hipErrorInvalidValue;
-  const dim3 grid((S / 128) * Hq * B), block(256);
-  const float sl2 = scale * 1.4426950408889634f;
-#define LAUNCH(DD, CC) \
-  hipLaunchKernelGGL((fwd_kernel<DD, CC>), grid, block, 0, st, q, k, v, o, lse, S, Hq, Hkv, ldq, ldk, ldv, ldo, sl2, skv)
-  if (D == 128) { if (causal) LAUNCH(128, true); else LAUNCH(128, false); }
-  else { if (causal) LAUNCH(64, true); else LAUNCH(64, false); }
-#undef LAUNCH
+static bool f32_shape_ok(const pra_attn_args& a, bool bwd) {
+  if (a.S % 128 || (a.D != 64 && a.D != 128) || a.Hq % a.Hkv || a.skv <= 0 || a.skv > a.S) return false;
+  return strides_ok(a, bwd, 4);
+}
+
+hipError_t f32_fwd(const pra_attn_args& a, hipStream_t st) {
+  if (!f32_shape_ok(a, false)) return hipErrorInvalidValue;
+  const dim3 grid((a.S / 128) * a.Hq * a.B), block(256);
+  const float sl2 = a.scale * kLog2e;
+  dispatch(
+      [&](auto d, auto c) {
+        hipLaunchKernelGGL((attnf::fwd_kernel<d(), c()>), grid, block, 0, st,
+                           (const float*)a.q, (const float*)a.k, (const float*)a.v, (float*)a.o, a.lse, a.S, a.Hq,
+                           a.Hkv, a.ldq, a.ldk, a.ldv, a.ldo, sl2, a.skv);
+      },
+      HeadDim{a.D}, Causal{a.causal != 0});
   return hipGetLastError();
 }
 
-hipError_t pra_attn_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* dout,
-                            const float* lse, float* delta, float* dq, float* dk, float* dv, int B, int S, int Hq,
-                            int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
-                            long lddv, float scale, int causal, int skv, hipStream_t st) {
-  using namespace pra::attnf;
-  if (S % 128 || (D != 64 && D != 128) || Hq % Hkv || skv <= 0 || skv > S) return hipErrorInvalidValue;
-  if (ldq % 4 || ldk % 4 || ldv % 4 || ldo % 4 || lddo % 4 || lddq % 4 || lddk % 4 || lddv % 4)
-    return hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
-  {  // dQ first: it writes delta
-    const dim3 grid((S / 128) * Hq * B);
-#define LAUNCH(DD, CC)                                                                                      \
-  hipLaunchKernelGGL((bwd_dq_kernel<DD, CC>), grid, dim3(256), 0, st, q, k, v, dout, o, lse, delta, dq, S, Hq, \
-                     Hkv, ldq, ldk, ldv, lddo, ldo, lddq, scale, sl2, skv)
-    if (D == 128) { if (causal) LAUNCH(128, true); else LAUNCH(128, false); }
-    else { if (causal) LAUNCH(64, true); else LAUNCH(64, false); }
-#undef LAUNCH
-  }
-  {
-    const dim3 grid((S / 128) * Hkv * B);
-#define LAUNCH(DD, CC)                                                                                         \
-  hipLaunchKernelGGL((bwd_dkdv_kernel<DD, CC>), grid, dim3(256), 0, st, q, k, v, dout, lse, delta, dk, dv, S, Hq, \
-                     Hkv, ldq, ldk, ldv, lddo, lddk, lddv, scale, sl2, skv)
-    if (D == 128) { if (causal) LAUNCH(128, true); else LAUNCH(128, false); }
-    else { if (causal) LAUNCH(64, true); else LAUNCH(64, false); }
-#undef LAUNCH
-  }
+// mid_event is not recorded here (pra_attn_bwd says why); the fp32 kernels have no fused inverse RoPE
+hipError_t f32_bwd(const pra_attn_args& a, hipStream_t st) {
+  if (a.rope_tab != nullptr || !f32_shape_ok(a, true)) return hipErrorInvalidValue;
+  const float *q = (const float*)a.q, *k = (const float*)a.k, *v = (const float*)a.v, *dout = (const float*)a.dout;
+  const float sl2 = a.scale * kLog2e;
+  float* delta = a.ws;  // BwdPlan::delta = 0 is the fp32 backward's whole layout
+  const HeadDim d_{a.D};
+  const Causal c_{a.causal != 0};
+  dispatch(  // dQ first: it writes delta
+      [&](auto d, auto c) {
+        hipLaunchKernelGGL((attnf::bwd_dq_kernel<d(), c()>),
+                           dim3((a.S / 128) * a.Hq * a.B), dim3(256), 0, st, q, k, v, dout, (const float*)a.o, a.lse,
+                           delta, (float*)a.dq, a.S, a.Hq, a.Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.ldo, a.lddq, a.scale,
+                           sl2, a.skv);
+      },
+      d_, c_);
+  dispatch(
+      [&](auto d, auto c) {
+        hipLaunchKernelGGL((attnf::bwd_dkdv_kernel<d(), c()>),
+                           dim3((a.S / 128) * a.Hkv * a.B), dim3(256), 0, st, q, k, v, dout, a.lse, delta,
+                           (float*)a.dk, (float*)a.dv, a.S, a.Hq, a.Hkv, a.ldq, a.ldk, a.ldv, a.lddo, a.lddk, a.lddv,
+                           a.scale, sl2, a.skv);
+      },
+      d_, c_);
   return hipGetLastError();
 }
 
-}  // extern "C"
+}  // namespace attn
+}  // namespace pra

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "attn_plan.h"
+
 extern "C" {
 int pra_rmsnorm_bwd_ws_extra();
 int pra_rmsnorm_bwd_ws_rows(int rows);
@@ -118,50 +120,42 @@ hipError_t pra_pull_gather(const void* const* srcs, void* const* dsts, const lon
 hipError_t pra_sparse_rows(int dtype, int phase, void* const* grads, const int64_t* const* ids, int W, int me, long n,
                            long V, long D, hipStream_t s);
 
-hipError_t pra_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq,
-                        int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal,
-                        int skv, hipStream_t st);
-// delta: fp32 workspace of 3 * B * Hq * S floats (delta and the pipelined dK/dV kernel's row constants)
-hipError_t pra_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                        const float* lse, float* delta, void* dq, void* dk, void* dv, int B, int S, int Hq, int Hkv,
-                        int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv,
-                        float scale, int causal, int skv, const float* rope_tab, hipEvent_t mid_event,
-                        hipStream_t st);
-void pra_attn_set_options(int fwd_pipe, float fwd_thr, int dkdv_impl, int dq_pipe, int dkdv_split, int dkdv_kreg,
-                          int bwd_fused, int bwd_window);
-// block order of the forward / dQ / dK/dV grids: 0 = heavy tiles first, G > 0 = XCD-grouped with G heads
-// per group, -1 = by shape (attention.hip block_tile)
-void pra_attn_set_order(int fwd, int dq, int dkdv);
-// fused dQ/dK/dV backward (attention_bwd_fused.hip); ws: 2 B Hq S row constants + B Hq S 128 dQ partials
-hipError_t pra_attn_bwd_fused(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                              const float* lse, float* ws, void* dq, void* dk, void* dv, int B, int S, int Hq,
-                              int Hkv, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
-                              long lddv, float scale, int causal, const float* rope_tab, hipEvent_t mid_event,
-                              hipStream_t st);
-// floats of fp32 workspace pra_attn_bwd needs at `delta` (delta, row constants, split dK/dV parts)
-long pra_attn_bwd_workspace(int dtype, int B, int S, int Hq, int Hkv, int D);
-// Document-masked causal attention (attention_docs.hip), bf16 / fp16, S % 128 == 0. doc_start int32
-// [B][S]: query i sees key j iff doc_start[b][i] <= j <= i (values clamped into [0, i]). ws: fp32
-// workspace of pra_attn_docs_bwd_workspace words. rope_tab: inverse RoPE on dq / dk at the packed
-// positions i - doc_start[b][i]; skv: real sequence length of a zero-padded one. mid_event is
-// recorded between the dQ and dK/dV kernels.
-hipError_t pra_attn_docs_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
-                             const int* doc_start, int B, int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv,
-                             long ldo, float scale, hipStream_t st);
-hipError_t pra_attn_docs_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout,
-                             const float* lse, float* ws, void* dq, void* dk, void* dv, const int* doc_start, int B,
-                             int S, int Hq, int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo,
-                             long lddq, long lddk, long lddv, float scale, int skv, const float* rope_tab,
-                             hipEvent_t mid_event, hipStream_t st);
-long pra_attn_docs_bwd_workspace(int B, int S, int Hq, int Hkv, int D);
-// fp32 flash attention (attention_f32.hip, f32-input MFMA); pra_attn_fwd / pra_attn_bwd route kF32 here
-hipError_t pra_attn_fwd_f32(const float* q, const float* k, const float* v, float* o, float* lse, int B, int S, int Hq,
-                            int Hkv, int D, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int skv,
-                            hipStream_t st);
-hipError_t pra_attn_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* dout,
-                            const float* lse, float* delta, float* dq, float* dk, float* dv, int B, int S, int Hq,
-                            int Hkv, int D, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
-                            long lddv, float scale, int causal, int skv, hipStream_t st);
+// Training attention (attention.hip and its siblings). Tensors are [B, S, H, D] views with a token
+// stride in elements (% 8 for bf16 / fp16, % 4 for fp32), so q / k / v can be slices of a fused QKV
+// activation; lse is fp32 [B, Hq, S]. The launchers read the block before they return and keep no
+// pointer to it (graph capture).
+typedef struct pra_attn_args {
+  int dtype;  // pra::DType: kF32 routes to the fp32 kernels (attention_f32.hip)
+  int B, S, Hq, Hkv, D;
+  int skv;     // real sequence length when S is zero-padded (keys >= skv are masked), else S
+  int causal;
+  float scale;
+  const void* q; long ldq;
+  const void* k; long ldk;
+  const void* v; long ldv;
+  void* o; long ldo;  // written by the forward, read by the backward
+  const void* dout; long lddo;
+  void* dq; long lddq;
+  void* dk; long lddk;
+  void* dv; long lddv;
+  float* lse;  // written by the forward, read by the backward
+  float* ws;   // backward: pra_attn_bwd_workspace floats
+  // The rest is optional. doc_start, int32 [B][S]: document-masked causal attention (attention_docs.hip,
+  // 16-bit, S % 128 == 0): query i sees key j iff doc_start[b][i] <= j <= i (values clamped into [0, i]).
+  // rope_tab (16-bit), fp32 [>= S][D / 2][2]: dq / dk are stored with the inverse rotation (with doc_start:
+  // at the packed positions i - doc_start[b][i]). mid_event: recorded once where a side-stream job may
+  // start beside the backward (BwdPlan::win_early; docs: between dQ and dK/dV; fp32: never).
+  const int* doc_start;
+  const float* rope_tab;
+  hipEvent_t mid_event;
+} pra_attn_args;
+hipError_t pra_attn_fwd(const pra_attn_args* a, hipStream_t st);
+hipError_t pra_attn_bwd(const pra_attn_args* a, hipStream_t st);
+// floats of fp32 workspace pra_attn_bwd needs at `ws` (shape, dtype and doc_start != null are read)
+long pra_attn_bwd_workspace(const pra_attn_args* a);
+// kernel selection (attn_plan.h); not thread-safe against concurrent launches (set between steps)
+void pra_attn_get_options(pra_attn_options* out);
+void pra_attn_set_options(const pra_attn_options* in);
 
 // KV-cache generation (attention_decode.hip), bf16 / fp16. Caches are [B][cap][Hkv][D] contiguous;
 // kv_len is int32 [B] on the device and is clamped by the kernels (no host copy is ever read).

@@ -64,7 +64,7 @@ def hip16(t) -> bool:
     return t.is_cuda and t.dtype in (torch.bfloat16, torch.float16)
 
 
-# Attention kernel selection (csrc/kernels/attention.hip AttnOptions): -1 = by shape. The launchers
+# Attention kernel selection (csrc/kernels/attn_plan.h pra_attn_options): -1 = by shape. The launchers
 # read no environment. set_attn_options() changes the options between launches (tests, A/B tools);
 # of the environment only PYRECOVER_ATTN_BWD_FUSED (the one experimental kernel path: the fused
 # deterministic backward) is read, once, when the extension loads -- every other option is a
@@ -100,9 +100,7 @@ def _attn_env() -> dict:
 def _apply_options(mod, env: dict) -> None:
     opts = dict(_attn_opts)
     opts.update(env)
-    mod.attn_set_options(opts["fwd_pipe"], opts["fwd_thr"], opts["dkdv_impl"], opts["dq_pipe"], opts["dkdv_split"],
-                         opts["dkdv_kreg"], opts["bwd_fused"], opts["bwd_window"])
-    mod.attn_set_order(opts["fwd_order"], opts["dq_order"], opts["dkdv_order"])
+    mod.attn_set_options(**opts)
     _attn_opts.update(opts)
 
 

@@ -142,3 +142,54 @@ def test_unsupported_head_dim_warns_once_and_stays_correct(cuda):
         F._attn_fwd(q, k, v, 96 ** -0.5, True)  # the second call is silent
     ref_o = R.attention_ref(q.float(), k.float(), v.float(), True, 96 ** -0.5)
     assert _rel(o, ref_o) < 1e-2
+
+
+def test_attention_bindings_reject_bad_operands(cuda):
+    """attn_fwd / attn_bwd refuse operands the kernels cannot take, each with its own message, before
+    anything is launched."""
+    C = _ext.native()
+    B, S, Hq, Hkv, D = 1, 128, 2, 1, 64
+    scale = D ** -0.5
+    q, k, v = _qkv(cuda, B, S, Hq, Hkv, D, torch.bfloat16)
+    o, lse = C.attn_fwd(q, k, v, scale, True)
+    do = torch.randn_like(o)
+    ds = torch.zeros(B, S, dtype=torch.int32, device=cuda)
+
+    def bwd(q=q, k=k, v=v, o=o, do=do, lse=lse, dq=None, rope_tab=None, doc_start=None, causal=True):
+        dq = torch.empty_like(q) if dq is None else dq
+        C.attn_bwd(q, k, v, o, do, lse, dq, torch.empty_like(k), torch.empty_like(v), scale, causal,
+                   rope_tab=rope_tab, doc_start=doc_start)
+
+    bwd()  # the operands above are good
+    with pytest.raises(RuntimeError, match="attention: k must be BFloat16 like q"):
+        C.attn_fwd(q, k.half(), v, scale, True)
+    with pytest.raises(RuntimeError, match="attention: k must be BFloat16 like q"):
+        bwd(k=k.half())
+    with pytest.raises(RuntimeError, match=r"attention: dq must be \[B, S, H, D\] = \[1, 128, 2, 64\]"):
+        bwd(dq=torch.empty(B, S, Hkv, D, dtype=q.dtype, device=cuda))
+    q2 = torch.randn(B, S, Hq, 2 * D, device=cuda).to(torch.bfloat16)[..., ::2]  # last stride 2
+    with pytest.raises(RuntimeError, match="attention: q must have token-major layout with contiguous heads"):
+        C.attn_fwd(q2, k, v, scale, True)
+    with pytest.raises(RuntimeError, match="attention: q must have token-major layout with contiguous heads"):
+        bwd(q=q2)
+    with pytest.raises(RuntimeError, match="attention: lse"):
+        bwd(lse=lse[:, :, :S - 1].contiguous())
+    q96, k96, v96 = _qkv(cuda, B, S, Hq, Hkv, 96, torch.bfloat16)
+    with pytest.raises(RuntimeError, match="attention: head_dim must be 64 or 128"):
+        C.attn_fwd(q96, k96, v96, scale, True)
+    with pytest.raises(RuntimeError, match="attention: head_dim must be 64 or 128"):
+        C.attn_bwd(q96, k96, v96, torch.empty_like(q96), torch.empty_like(q96), lse, torch.empty_like(q96),
+                   torch.empty_like(k96), torch.empty_like(v96), scale, True)
+    with pytest.raises(RuntimeError, match="attention: doc_start implies causal attention"):
+        C.attn_fwd(q, k, v, scale, False, doc_start=ds)
+    with pytest.raises(RuntimeError, match="attention: doc_start implies causal attention"):
+        bwd(doc_start=ds, causal=False)
+    with pytest.raises(RuntimeError, match=r"attention: doc_start must be contiguous int32 \[B, S\]"):
+        C.attn_fwd(q, k, v, scale, True, doc_start=ds.long())
+    with pytest.raises(RuntimeError, match=r"attention: doc_start must be contiguous int32 \[B, S\]"):
+        bwd(doc_start=ds.long())
+    tab = torch.zeros(S, D // 2, 2, device=cuda)
+    f = [t.float().contiguous() for t in (q, k, v, o, do)]
+    with pytest.raises(RuntimeError, match="attention: the fp32 backward has no fused inverse RoPE"):
+        C.attn_bwd(*f, lse, torch.empty_like(f[0]), torch.empty_like(f[1]), torch.empty_like(f[2]), scale, True,
+                   rope_tab=tab)

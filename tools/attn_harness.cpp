@@ -75,31 +75,33 @@ int main(int argc, char** argv) {
   // PRA_BWD_FUSED=0/1: split dQ + dK/dV kernels or the fused backward; PRA_FWD_PIPE=0/1: forward
   // kernel (fwd_kernel / pipelined fwd_p_kernel); unset = the defaults
   {
+    pra_attn_options op;
+    pra_attn_get_options(&op);
     const char* f = getenv("PRA_FWD_PIPE");
     const char* e = getenv("PRA_BWD_FUSED");
-    if (f || e) pra_attn_set_options(f ? atoi(f) : -1, 8.f, -1, -1, 1, -2, e ? atoi(e) : 0, 0);
-    // PRA_ATTN_ORDER="f,q,k": block order of the forward / dQ / dK/dV grids (pra_attn_set_order)
-    int of = 0, oq = 0, ok = 0;
-    if (const char* o = getenv("PRA_ATTN_ORDER")) sscanf(o, "%d,%d,%d", &of, &oq, &ok);
-    pra_attn_set_order(of, oq, ok);
+    if (f) op.fwd_pipe = atoi(f);
+    if (e) op.bwd_fused = atoi(e);
+    // PRA_ATTN_ORDER="f,q,k": block order of the forward / dQ / dK/dV grids
+    if (const char* o = getenv("PRA_ATTN_ORDER")) sscanf(o, "%d,%d,%d", &op.fwd_order, &op.dq_order, &op.dkdv_order);
+    pra_attn_set_options(&op);
   }
-  const long nws = pra_attn_bwd_workspace(pra::kBF16, B, S, Hq, Hkv, D);
-  CK(hipMalloc(&ws, (size_t)nws * 4));
+  pra_attn_args a = {};
+  a.dtype = pra::kBF16;
+  a.B = B, a.S = S, a.Hq = Hq, a.Hkv = Hkv, a.D = D, a.skv = S, a.causal = causal;
+  a.scale = 1.f / std::sqrt((float)D);
+  a.q = qkv, a.k = qkv + (long)Hq * D, a.v = qkv + (long)(Hq + Hkv) * D, a.ldq = a.ldk = a.ldv = ldqkv;
+  a.o = o, a.dout = dout, a.dq = dq, a.ldo = a.lddo = a.lddq = ldo;
+  a.dk = dk, a.dv = dv, a.lddk = a.lddv = (long)Hkv * D;
+  a.lse = lse;
+  CK(hipMalloc(&ws, (size_t)pra_attn_bwd_workspace(&a) * 4));
+  a.ws = ws;
   CK(hipMemcpy(qkv, h_qkv.data(), nqkv * 2, hipMemcpyHostToDevice));
   CK(hipMemcpy(dout, h_do.data(), no * 2, hipMemcpyHostToDevice));
-  const uint16_t* q = qkv;
-  const uint16_t* k = qkv + (long)Hq * D;
-  const uint16_t* v = qkv + (long)(Hq + Hkv) * D;
-  const float scale = 1.f / std::sqrt((float)D);
+  const float scale = a.scale;
   hipStream_t st;
   CK(hipStreamCreate(&st));
-  auto fwd = [&] {
-    CK(pra_attn_fwd(pra::kBF16, q, k, v, o, lse, B, S, Hq, Hkv, D, ldqkv, ldqkv, ldqkv, ldo, scale, causal, S, st));
-  };
-  auto bwd = [&] {
-    CK(pra_attn_bwd(pra::kBF16, q, k, v, o, dout, lse, ws, dq, dk, dv, B, S, Hq, Hkv, D, ldqkv, ldqkv, ldqkv, ldo, ldo,
-                    ldo, (long)Hkv * D, (long)Hkv * D, scale, causal, S, nullptr, nullptr, st));
-  };
+  auto fwd = [&] { CK(pra_attn_fwd(&a, st)); };
+  auto bwd = [&] { CK(pra_attn_bwd(&a, st)); };
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
