@@ -1025,6 +1025,90 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cac
   return {o, lse};
 }
 
+// Device-side sampling (csrc/kernels/sample.hip): logits [B, V] bf16 / fp16 (row stride >= V) -> tok int64 [B].
+// temperature 0 is greedy; otherwise pos (int32 [B]) or, with the generation state, prompt_len + count
+// indexes the Philox draw. ws: int32 workspace of sample_ws_bytes(B) bytes (allocated here when absent).
+// The generation state (done uint8, count / room int32 [B], out int64 [B, max_new]) is given whole or not
+// at all.
+void sample_(const at::Tensor& logits, at::Tensor tok, double temperature, int64_t top_k, double top_p, int64_t seed,
+             const c10::optional<at::Tensor>& pos, c10::optional<at::Tensor> ws, c10::optional<at::Tensor> u_out,
+             c10::optional<at::Tensor> done, c10::optional<at::Tensor> count, const c10::optional<at::Tensor>& room,
+             c10::optional<at::Tensor> out, int64_t eos_id, const c10::optional<at::Tensor>& prompt_len) {
+  const Range range_("pyrecover::sample");
+  check_dev(logits, "logits");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kHalf,
+              "sample: the HIP kernel takes bf16 or fp16 logits (got ", logits.scalar_type(),
+              "); other dtypes run pyrecover_amd.ops.reference.sample_philox_ref");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0, "sample: logits must be [B, V], got ",
+              logits.sizes());
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(B <= 65535 && V <= (int64_t(1) << 30), "sample: B <= 65535 and V <= 2^30");
+  TORCH_CHECK((V == 1 || logits.stride(1) == 1) && (B == 1 || logits.stride(0) >= V),
+              "sample: logits need unit inner stride and a row stride >= V");
+  const int64_t ld = B == 1 ? V : logits.stride(0);
+  TORCH_CHECK(temperature >= 0.0 && temperature <= 3.0e38, "sample: temperature must be finite and >= 0, got ",
+              temperature);
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "sample: top_p must be in (0, 1], got ", top_p);
+  TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, "sample: top_k must be >= 0, got ", top_k);
+  auto vec = [&](const at::Tensor& t, at::ScalarType ty, const char* name) {
+    same_dev(logits, t, name);
+    TORCH_CHECK(t.scalar_type() == ty && t.dim() == 1 && t.size(0) == B && t.is_contiguous(), "sample: ", name,
+                " must be contiguous ", ty, " [B]");
+  };
+  vec(tok, at::kLong, "tok");
+  pra_sample_args a = {};
+  a.temperature = (float)temperature;
+  a.top_k = (int)top_k;
+  a.top_p = (float)top_p;
+  TORCH_CHECK(temperature == 0.0 || a.temperature > 0.f, "sample: temperature underflows fp32");
+  TORCH_CHECK(a.top_p > 0.f, "sample: top_p underflows fp32");
+  a.seed = (unsigned long long)seed;
+  a.tok = (long long*)tok.data_ptr<int64_t>();
+  const bool stateful = done.has_value();
+  TORCH_CHECK(count.has_value() == stateful && room.has_value() == stateful && out.has_value() == stateful,
+              "sample: done, count, room and out are given together or not at all");
+  TORCH_CHECK(stateful || !prompt_len.has_value(), "sample: prompt_len needs the generation state");
+  if (stateful) {
+    vec(*done, at::kByte, "done");
+    vec(*count, at::kInt, "count");
+    vec(*room, at::kInt, "room");
+    same_dev(logits, *out, "out");
+    TORCH_CHECK(out->scalar_type() == at::kLong && out->dim() == 2 && out->size(0) == B && out->size(1) > 0 &&
+                    out->size(1) <= INT32_MAX && out->is_contiguous(),
+                "sample: out must be contiguous int64 [B, max_new]");
+    a.gen.done = done->data_ptr<uint8_t>();
+    a.gen.count = count->data_ptr<int>();
+    a.gen.room = room->data_ptr<int>();
+    a.gen.out = (long long*)out->data_ptr<int64_t>();
+    a.gen.max_new = (int)out->size(1);
+    a.gen.eos_id = eos_id;
+    if (prompt_len.has_value()) {
+      vec(*prompt_len, at::kInt, "prompt_len");
+      a.gen.prompt_len = prompt_len->data_ptr<int>();
+    }
+  }
+  const c10::DeviceGuard guard(logits.device());
+  if (temperature > 0.0) {
+    TORCH_CHECK(pos.has_value() || prompt_len.has_value(), "sample: a draw needs pos (or prompt_len with the state)");
+    if (pos.has_value()) {
+      vec(*pos, at::kInt, "pos");
+      a.pos = pos->data_ptr<int>();
+    }
+    const int64_t need = pra_sample_ws_bytes((int)B);
+    if (!ws.has_value()) ws = at::empty({need / 4}, logits.options().dtype(at::kInt));
+    same_dev(logits, *ws, "ws");
+    TORCH_CHECK(ws->scalar_type() == at::kInt && ws->is_contiguous() && ws->numel() * 4 >= need &&
+                    reinterpret_cast<uintptr_t>(ws->data_ptr()) % 16 == 0,
+                "sample: ws must be contiguous, 16-B aligned int32 with at least ", need, " bytes");
+    a.ws = (unsigned*)ws->data_ptr<int>();
+    if (u_out.has_value()) {
+      vec(*u_out, at::kFloat, "u_out");
+      a.u_out = u_out->data_ptr<float>();
+    }
+  }
+  check(pra_sample(dt(logits), logits.data_ptr(), ld, (int)B, (int)V, &a, stream_of(logits)), "sample");
+}
+
 // Writes dq/dk/dv into caller-provided [B,S,H,D] views (e.g. slices of a fused dQKV buffer).
 void attn_bwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
               const at::Tensor& dout, const at::Tensor& lse, at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale,
@@ -1156,6 +1240,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"));
   m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
+  m.def("sample_", &sample_, py::arg("logits"), py::arg("tok"), py::arg("temperature"), py::arg("top_k"),
+        py::arg("top_p"), py::arg("seed"), py::arg("pos") = py::none(), py::arg("ws") = py::none(),
+        py::arg("u_out") = py::none(), py::arg("done") = py::none(), py::arg("count") = py::none(),
+        py::arg("room") = py::none(), py::arg("out") = py::none(), py::arg("eos_id") = -1,
+        py::arg("prompt_len") = py::none());
+  m.def("sample_ws_bytes", [](int B) { return pra_sample_ws_bytes(B); });
   // every field of pra_attn_options (csrc/kernels/attn_plan.h documents them), by keyword
   m.def("attn_set_options", [](int fwd_pipe, double fwd_thr, int dkdv_impl, int dq_pipe, int dkdv_split, int dkdv_kreg,
                                int bwd_fused, int bwd_window, int fwd_order, int dq_order, int dkdv_order) {

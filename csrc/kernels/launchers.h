@@ -170,4 +170,36 @@ hipError_t pra_attn_decode(int dtype, const void* q, const void* k_cache, const 
                            hipStream_t s);
 long pra_attn_decode_ws_floats(int B, int Hq, int D, int cap);
 int pra_attn_decode_chunk();
+
+// Device-side sampling (sample.hip documents the rule), bf16 / fp16 logits [B][ld], ld >= V >= 1, no
+// alignment demand beyond the element. The launcher copies the block before it returns (graph capture).
+// The generation state is optional (done == null: absent). With it the launch also does the bookkeeping
+// of inference.generate: a row with done[b] set writes nothing but tok[b] = 0; any other row stores its
+// token at out[b][count[b]], increments count[b], and sets done[b] when the token is eos_id or
+// count[b] > room[b] (room: cache rows the sequence had left after its prompt; the token that finds the
+// cache full is still emitted). tok[b] of a row that finished in this launch is 0 too: tok is the next
+// decode step's input.
+typedef struct pra_sample_state {
+  unsigned char* done;    // uint8 [B]
+  int* count;             // int32 [B]: tokens emitted so far
+  const int* room;        // int32 [B]
+  long long* out;         // int64 [B][max_new]
+  int max_new;
+  long long eos_id;       // -1: none
+  const int* prompt_len;  // optional int32 [B]: the draw's position is prompt_len[b] + count[b], not pos[b]
+} pra_sample_state;
+typedef struct pra_sample_args {
+  float temperature;  // 0: greedy under NaN < -inf < finite < +inf, ties to the lowest id; no Philox call
+  int top_k;          // 0: off
+  float top_p;        // in (0, 1]
+  unsigned long long seed;
+  const int* pos;     // int32 [B]: absolute position the sampled token will occupy (Philox counter word 1)
+  long long* tok;     // int64 [B], output
+  float* u_out;       // optional fp32 [B]: the uniform each row drew (temperature > 0)
+  unsigned* ws;       // pra_sample_ws_bytes(B) bytes, 16-B aligned, any contents (temperature > 0)
+  pra_sample_state gen;
+} pra_sample_args;
+long pra_sample_ws_bytes(int B);
+hipError_t pra_sample(int dtype, const void* logits, long ld, int B, int V, const pra_sample_args* args,
+                      hipStream_t s);
 }

@@ -1,7 +1,8 @@
 """``generate.py`` command line: sample from a checkpoint written by ``train.py``.
 
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
-        --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl
+        --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
+        [--sampler philox --decode-graph]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
 ``--model-dtype``, ``--tokenizer-name-or-path``) and the checkpoint flags (``--checkpoint-dir``,
@@ -63,6 +64,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy (ties to the lowest token id)")
     p.add_argument("--top-k", type=int, default=0, help="0: off")
     p.add_argument("--top-p", type=float, default=1.0, help="1: off")
+    p.add_argument("--sampler", choices=("torch", "philox"), default="torch",
+                   help="torch: torch.multinomial with a seeded generator. philox: the stateless rule of "
+                        "csrc/kernels/sample.hip, a draw is a function of (seed, prompt, position); one kernel "
+                        "launch per token on a bf16 / fp16 GPU model")
+    p.add_argument("--decode-graph", action="store_true",
+                   help="replay sample + decode step as one hipGraph per token (needs --sampler philox or "
+                        "--temperature 0, and a bf16 / fp16 GPU model)")
     p.add_argument("--no-kv-cache", action="store_true",
                    help="naive path: a full forward over the whole prefix per new token (debugging aid)")
     p.add_argument("--output-jsonl", type=str, default=None,
@@ -96,13 +104,13 @@ def main(argv=None) -> int:
     stats = {}
     tokens, reasons = generate(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                top_p=args.top_p, seed=args.seed, eos_id=eos, use_cache=not args.no_kv_cache,
-                               stats=stats)
+                               stats=stats, sampler=args.sampler, graph=args.decode_graph)
     records = []
     for p, ids, why in zip(prompts, tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None
         records.append({"prompt_ids": list(p), "generated_ids": ids, "text": text, "finish_reason": why,
                         "prefill_ms": stats["prefill_ms"], "decode_ms_per_token": stats["decode_ms_per_token"],
-                        "checkpoint_step": step})
+                        "checkpoint_step": step, "sampler": args.sampler, "decode_graph": args.decode_graph})
         logger.info(f"[{why}] {ids if text is None else text!r}")
     if args.output_jsonl:
         with open(args.output_jsonl, "w", encoding="utf-8") as f:

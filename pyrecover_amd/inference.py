@@ -12,6 +12,14 @@ argument depends on a host copy of it: a decode step never synchronises.
 The HIP decode kernels take bf16 / fp16 at head_dim 64 / 128. CPU tensors, fp32 / fp64 models on the
 GPU and other head dims run the torch math of :mod:`pyrecover_amd.ops.reference`
 (``attention_decode_ref`` / ``rope_append_ref``), noted once through ``_note_fallback`` like attention.
+
+Sampling has two rules. ``sampler="torch"`` (the default) filters with ``torch.topk`` / ``torch.sort`` and
+draws with ``torch.multinomial`` from a seeded ``torch.Generator``. ``sampler="philox"`` is the stateless
+rule of csrc/kernels/sample.hip (:func:`sample_philox`): the uniform of a draw is a Philox function of
+(seed, row, absolute position), so tokens do not depend on how many were drawn before, and the kernel
+also keeps ``out`` / ``count`` / ``done`` on the device (:class:`DeviceSampler`). With it nothing in a
+token's work depends on the host, and :class:`DecodeGraph` replays sample -> ``decode_step`` as one
+hipGraph (``generate(graph=True)``).
 """
 from __future__ import annotations
 
@@ -233,10 +241,124 @@ def _model_device_dtype(model):
     return w.device, w.dtype
 
 
+def _seed64(seed: int) -> int:
+    """Any Python int as the signed 64-bit value the binding takes (the kernel reads it as unsigned)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+def sample_philox(logits: torch.Tensor, pos: torch.Tensor, temperature: float = 0.0, top_k: int = 0,
+                  top_p: float = 1.0, seed: int = 0) -> torch.Tensor:
+    """Next token ids [B] from logits [B, V] by the stateless rule (``ops/reference.py::sample_philox_ref``
+    documents it): row b draws with the Philox uniform of (seed, b, pos[b]), ``pos[b]`` being the absolute
+    position the token will occupy. bf16 / fp16 logits on the GPU run the HIP kernel, everything else the
+    torch rule."""
+    if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise ValueError("sample_philox: need temperature >= 0, 0 < top_p <= 1, top_k >= 0")
+    if not _ext.hip16(logits):
+        return ref.sample_philox_ref(logits, pos, temperature, top_k, top_p, seed)
+    tok = torch.empty(logits.shape[0], dtype=torch.long, device=logits.device)
+    pos = pos.to(device=logits.device, dtype=torch.int32).contiguous()
+    _ext.require_for(logits).sample_(logits, tok, temperature, top_k, top_p, _seed64(seed), pos=pos)
+    return tok
+
+
+class DeviceSampler:
+    """The sampling kernel with the generation state of one ``generate`` call on the device: ``out`` int64
+    [B, max_new] (-1 where nothing was written), ``count`` int32 [B], ``done`` uint8 [B] and ``tok`` int64
+    [B], the next decode step's input (0 for finished rows). ``room`` [B] is the number of cache rows a
+    sequence has left after its prompt: the token that finds the cache full is emitted and finishes the
+    row. One :meth:`sample` is one launch and reads nothing from the host; draws are indexed by
+    ``prompt_len + count``. bf16 / fp16 logits on the GPU only."""
+
+    def __init__(self, prompt_len: torch.Tensor, room: torch.Tensor, max_new_tokens: int, temperature: float = 0.0,
+                 top_k: int = 0, top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None):
+        if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
+            raise ValueError("DeviceSampler: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
+        dev = prompt_len.device
+        B = prompt_len.numel()
+        self.C = _ext.require_for(prompt_len)
+        self.args = (float(temperature), int(top_k), float(top_p), _seed64(seed))
+        self.eos_id = -1 if eos_id is None else int(eos_id)
+        self.prompt_len = prompt_len.to(torch.int32).contiguous()
+        self.room = room.to(device=dev, dtype=torch.int32).contiguous()
+        self.out = torch.full((B, max_new_tokens), -1, dtype=torch.long, device=dev)
+        self.count = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.tok = torch.zeros(B, dtype=torch.long, device=dev)
+        self.ws = (torch.empty(self.C.sample_ws_bytes(B) // 4, dtype=torch.int32, device=dev)
+                   if temperature > 0 else None)
+
+    def sample(self, logits: torch.Tensor) -> torch.Tensor:
+        self.C.sample_(logits, self.tok, *self.args, ws=self.ws, done=self.done, count=self.count, room=self.room,
+                       out=self.out, eos_id=self.eos_id, prompt_len=self.prompt_len)
+        return self.tok
+
+    def all_done(self) -> bool:
+        """Reads the finished mask back: a host synchronisation."""
+        return bool(self.done.all().item())
+
+
+class DecodeGraph:
+    """One generated token per :meth:`step`: sample from the static ``logits`` buffer, ``decode_step`` the
+    token, copy the new logits into the buffer. The first ``WARMUP`` steps run eagerly (library warm-up and
+    GEMM tuning; their tokens are real), the next one captures the body into a hipGraph on one stream
+    (a linear graph: the body forks no stream) and every step from there on is one replay. Temperature,
+    top-k, top-p and the seed are constants of the capture; every per-token quantity (``kv_len``, the
+    position of the draw, the finished mask) is read from device memory, so eager steps and replays give
+    the same bits."""
+
+    WARMUP = 2
+
+    def __init__(self, model, cache: KVCache, logits: torch.Tensor, sampler: DeviceSampler):
+        if not (_ext.hip16(logits) and model.model_args.head_dim in (64, 128)):
+            raise ValueError("DecodeGraph needs a bf16 / fp16 GPU model on the HIP decode path (head_dim 64 or 128)")
+        self.model, self.cache, self.sampler = model, cache, sampler
+        self.logits = logits.detach().clone().contiguous()
+        self.graph = None
+        self.steps = 0
+
+    @property
+    def captured(self) -> bool:
+        return self.graph is not None
+
+    def _body(self):
+        tok = self.sampler.sample(self.logits)
+        self.logits.copy_(decode_step(self.model, tok, self.cache))
+
+    def step(self) -> None:
+        if self.steps < self.WARMUP:
+            self._body()
+        else:
+            if self.graph is None:
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()  # eager-step blocks are not reusable by the graph's private pool
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):  # records without executing: the replay below runs this step
+                    self._body()
+                self.graph = g
+            self.graph.replay()
+        self.steps += 1
+
+
+def _graph_refusal(model, device, dtype, sampler: str, temperature: float, use_cache: bool) -> Optional[str]:
+    if sampler != "philox" and temperature != 0.0:
+        return ("sampler='torch' draws with a torch.Generator, whose state lives outside a graph: use "
+                "sampler='philox' or temperature 0")
+    if not use_cache:
+        return "the captured step is the KV-cache decode step: use_cache=False cannot be captured"
+    if device.type != "cuda" or dtype not in (torch.bfloat16, torch.float16):
+        return f"the captured step runs the HIP kernels: a bf16 / fp16 model on the GPU, not {dtype} on {device.type}"
+    if model.model_args.head_dim not in (64, 128):
+        return f"the HIP decode kernels take head_dim 64 or 128, not {model.model_args.head_dim}"
+    return None
+
+
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
-             stats: Optional[Dict] = None) -> Tuple[List[List[int]], List[str]]:
+             stats: Optional[Dict] = None, sampler: str = "torch",
+             graph: bool = False) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -246,10 +368,24 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     The finished mask lives on the device and is read back at most once per 16 generated tokens.
     ``use_cache=False`` is the naive path (a full ``model(tokens)`` per new token): a debugging aid and
     a second opinion. ``stats`` (a dict, optional) receives ``prefill_ms`` and ``decode_ms_per_token``
-    from device events on a GPU model (wall clock on the CPU)."""
+    from device events on a GPU model (wall clock on the CPU).
+
+    ``sampler="philox"`` draws by the stateless rule of :func:`sample_philox` instead: the token at
+    absolute position n of row b is a function of (seed, b, n) and the logits alone, on any device and on
+    both the cache and the naive path. On a bf16 / fp16 GPU model with the cache, sampling and the
+    bookkeeping are one kernel launch per token (:class:`DeviceSampler`). ``graph=True`` also replays
+    sample -> ``decode_step`` as a hipGraph (:class:`DecodeGraph`); it needs ``sampler="philox"`` or
+    temperature 0 and a bf16 / fp16 GPU model on the HIP decode path, and raises ``ValueError`` with the
+    reason otherwise."""
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
+    if sampler not in ("torch", "philox"):
+        raise ValueError(f"generate: sampler must be 'torch' or 'philox', got {sampler!r}")
     device, dtype = _model_device_dtype(model)
+    if graph:
+        why = _graph_refusal(model, device, dtype, sampler, temperature, use_cache)
+        if why is not None:
+            raise ValueError("generate: graph=True refused: " + why)
     args = model.model_args
     B = len(prompts)
     lens_host = [len(p) for p in prompts]
@@ -266,9 +402,11 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     lens = torch.tensor(lens_host, dtype=torch.long, device=device)
     room = cap - lens  # [B]: tokens a sequence can still append
     gen = None
-    if temperature > 0:
+    if temperature > 0 and sampler == "torch":
         gen = torch.Generator(device=device)
         gen.manual_seed(int(seed))
+    # sampling and bookkeeping in one launch per token: the philox rule (or greedy, for a graph) on 16-bit GPU logits
+    on_device = use_cache and _ext.hip16(model.tok_embeddings.weight) and (sampler == "philox" or graph)
 
     timer = _Timer(device)
     timer.mark()
@@ -280,37 +418,60 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         logits = model(buf[:, :S])[bi, lens - 1]
     timer.mark()
 
-    out = torch.full((B, max_new_tokens), -1, dtype=torch.long, device=device)
-    count = torch.zeros(B, dtype=torch.long, device=device)
-    done = torch.zeros(B, dtype=torch.bool, device=device)
     steps = 0
-    for i in range(max_new_tokens):
-        tok = sample_token(logits, temperature, top_k, top_p, gen)
-        out[:, i] = torch.where(done, out[:, i], tok)
-        count += (~done).long()
-        if eos_id is not None:
-            done = done | (tok == eos_id)
-        done = done | (room <= i)  # token i was the last this sequence has a cache row for
-        if i + 1 == max_new_tokens:
-            break
-        if (i + 1) % SYNC_EVERY == 0 and bool(done.all().item()):
-            break
-        tok = torch.where(done, torch.zeros_like(tok), tok)
-        if use_cache:
-            logits = decode_step(model, tok, cache)
-        else:
-            col = (lens + i).clamp(max=cap - 1)
-            keep = buf.gather(1, col[:, None])[:, 0]
-            buf.scatter_(1, col[:, None], torch.where(done, keep, tok)[:, None])
-            L = min(S + i + 1, cap)
-            logits = model(buf[:, :L])[bi, (lens + i + 1).clamp(max=L) - 1]
-        steps += 1
+    if on_device:
+        dsamp = DeviceSampler(lens, room, max_new_tokens, temperature, top_k, top_p, seed, eos_id)
+        dgraph = DecodeGraph(model, cache, logits, dsamp) if graph else None
+        for i in range(max_new_tokens):
+            if i + 1 == max_new_tokens:
+                dsamp.sample(dgraph.logits if graph else logits)  # the last token needs no decode step after it
+                break
+            if graph:
+                dgraph.step()
+            else:
+                tok = dsamp.sample(logits)
+                if (i + 1) % SYNC_EVERY == 0 and dsamp.all_done():
+                    break
+                logits = decode_step(model, tok, cache)
+            steps += 1
+            if graph and (i + 1) % SYNC_EVERY == 0 and dsamp.all_done():
+                break
+        out, count = dsamp.out, dsamp.count
+    else:
+        out = torch.full((B, max_new_tokens), -1, dtype=torch.long, device=device)
+        count = torch.zeros(B, dtype=torch.long, device=device)
+        done = torch.zeros(B, dtype=torch.bool, device=device)
+        for i in range(max_new_tokens):
+            if sampler == "philox":  # the token lands at absolute position lens + i (finished rows: unused)
+                tok = sample_philox(logits, lens + i, temperature, top_k, top_p, seed)
+            else:
+                tok = sample_token(logits, temperature, top_k, top_p, gen)
+            out[:, i] = torch.where(done, out[:, i], tok)
+            count += (~done).long()
+            if eos_id is not None:
+                done = done | (tok == eos_id)
+            done = done | (room <= i)  # token i was the last this sequence has a cache row for
+            if i + 1 == max_new_tokens:
+                break
+            if (i + 1) % SYNC_EVERY == 0 and bool(done.all().item()):
+                break
+            tok = torch.where(done, torch.zeros_like(tok), tok)
+            if use_cache:
+                logits = decode_step(model, tok, cache)
+            else:
+                col = (lens + i).clamp(max=cap - 1)
+                keep = buf.gather(1, col[:, None])[:, 0]
+                buf.scatter_(1, col[:, None], torch.where(done, keep, tok)[:, None])
+                L = min(S + i + 1, cap)
+                logits = model(buf[:, :L])[bi, (lens + i + 1).clamp(max=L) - 1]
+            steps += 1
     timer.mark()
     if stats is not None:
         t = timer.intervals_ms()
         stats["prefill_ms"] = t[0]
         stats["decode_ms_per_token"] = t[1] / steps if steps else 0.0
         stats["decode_steps"] = steps
+        stats["graph_replays"] = max(0, dgraph.steps - DecodeGraph.WARMUP) if graph else 0
 
     out_h, count_h = out.cpu(), count.cpu().tolist()
     tokens, reasons = [], []

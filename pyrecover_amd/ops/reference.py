@@ -247,3 +247,78 @@ def rope_append_ref(qkv, tab, kv_len, k_cache, v_cache) -> None:
     bi = torch.arange(B, device=qkv.device)
     k_cache[bi, pos] = rot[:, nq:].view(B, Hkv, D)
     v_cache[bi, pos] = qkv[:, nq + nk:].view(B, Hkv, D)
+
+
+# ---------------------------------------------------------------------------------------
+# Sampling (pyrecover_amd/inference.py; HIP: csrc/kernels/sample.hip)
+SAMPLE_STREAM = 3  # Philox counter word 3: after the stochastic-rounding streams 0, 1, 2 (optim/sr.py)
+
+
+def sample_uniform(pos: torch.Tensor, seed: int) -> torch.Tensor:
+    """The uniform in [0, 1) of the draw of row b at absolute position pos[b] (fp64, exact):
+    ``(philox4x32_10((b, pos[b], 0, 3), seed)[0] >> 8) * 2^-24``. A pure function of (seed, row, position)."""
+    from ..optim.sr import philox4x32_10
+
+    pos = torch.as_tensor(pos).to(torch.int64).reshape(-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    rows = torch.arange(pos.numel(), device=pos.device)
+    w0 = philox4x32_10((rows, pos & 0xFFFFFFFF, 0, SAMPLE_STREAM), (seed & 0xFFFFFFFF, seed >> 32))[0]
+    return (w0 >> 8).to(torch.float64) * 2.0 ** -24
+
+
+def greedy_total_order(logits: torch.Tensor) -> torch.Tensor:
+    """The lowest id holding the row maximum under NaN < -inf < finite < +inf. On rows without a NaN this
+    is ``inference.greedy_token``."""
+    V = logits.shape[-1]
+    nan = torch.isnan(logits)
+    xs = logits.masked_fill(nan, float("-inf"))
+    top = xs.max(dim=-1, keepdim=True).values
+    holds = (xs == top) & (~nan | nan.all(dim=-1, keepdim=True))
+    ids = torch.arange(V, device=logits.device).expand_as(logits)
+    return torch.where(holds, ids, V).min(dim=-1).values.clamp_(max=V - 1)
+
+
+def sample_philox_ref(logits: torch.Tensor, pos, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                      seed: int = 0) -> torch.Tensor:
+    """Token ids [B] from logits [B, V] by the rule of csrc/kernels/sample.hip, in torch (opmath: the
+    input's precision promoted to at least fp32): the CPU path, the path of fp32 / fp64 logits on the GPU.
+
+    Tokens are ranked by z = x / T descending, ties by ascending id (a stable sort). top-k keeps every
+    token with z >= the k-th largest z. top-p keeps the shortest prefix of the ranking whose softmax mass
+    over the top-k survivors reaches top_p (a token is dropped iff the mass ranked above it is >= top_p;
+    the first always stays). The draw is the first kept token whose cumulative mass exceeds
+    u * (kept mass), the last kept token if rounding leaves none, u = sample_uniform(pos, seed)[b].
+    A row whose maximum is not finite, and ``temperature == 0`` (no Philox call), give
+    :func:`greedy_total_order`."""
+    if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0:
+        raise ValueError("sample_philox_ref: need temperature >= 0, 0 < top_p <= 1, top_k >= 0")
+    x = up(logits)
+    B, V = x.shape
+    first = greedy_total_order(x)
+    if temperature == 0.0:
+        return first
+    u = sample_uniform(torch.as_tensor(pos).to(x.device), seed).to(x.dtype)
+    xs = x.masked_fill(torch.isnan(x), float("-inf"))
+    sz, si = torch.sort(xs / temperature, dim=-1, descending=True, stable=True)
+    keep = torch.ones_like(sz, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = sz >= sz[:, top_k - 1:top_k]
+    finite = torch.isfinite(sz[:, 0])
+    w = torch.exp(sz - sz[:, :1].masked_fill(~finite[:, None], 0.0))
+    w = torch.where(keep & torch.isfinite(w), w, torch.zeros_like(w))
+    zero = torch.zeros(B, 1, dtype=w.dtype, device=w.device)
+    if top_p < 1.0:
+        cum = torch.cumsum(w, dim=-1)
+        before = torch.cat([zero, cum[:, :-1]], dim=-1)
+        drop = before >= top_p * cum[:, -1:]
+        drop[:, 0] = False
+        keep = keep & ~drop
+        w = torch.where(keep, w, torch.zeros_like(w))
+    cum = torch.cumsum(w, dim=-1)
+    rank = torch.arange(V, device=x.device).expand(B, V)
+    hit = keep & (cum > u[:, None] * cum[:, -1:])
+    idx = torch.where(hit, rank, V).min(dim=-1).values
+    last = torch.where(keep, rank, -1).max(dim=-1).values
+    idx = torch.where(idx < V, idx, last)
+    tok = si.gather(1, idx[:, None])[:, 0]
+    return torch.where(finite, tok, first)

@@ -10,6 +10,16 @@ Every timed call reads another layer's cache (as a decode step does), and the la
 256 MiB Infinity Cache, so the rate is an HBM rate and not a cache-hit rate.
 
     python tools/decode_bench.py [--layers 4] [--iters 50] [--skip-step] [--shapes 7b,llama3-8b]
+    python tools/decode_bench.py --shapes 7b --sampler both --graph     # whole tokens: sample + bookkeeping + step
+    python tools/decode_bench.py --sample-bench                         # the sampler alone
+
+``--sampler torch|philox|both`` times whole generated tokens (sampling, the bookkeeping of ``generate`` and the
+decode step) per arm: ``torch`` is generate()'s default loop (``sample_token`` with a ``torch.Generator`` and
+the out / count / done updates as torch ops), ``philox`` the one-launch ``DeviceSampler``; ``--graph`` adds the
+philox arm replayed as a hipGraph (``DecodeGraph``). Temperature 0.8, top-k 50, top-p 0.95. One process per
+shape keeps the arms on one allocator and one set of tuned GEMMs. ``--sample-bench`` times ``sample_`` against
+``filter_logits`` + ``torch.multinomial`` on random bf16 logits (and on an all-equal row, the worst case for
+histogram contention).
 
 The times are device events around back-to-back calls: at batch 1 a call (two small kernels plus the
 binding's allocations) can cost the host more than the kernels take, so read the kernels' own time from a
@@ -95,16 +105,116 @@ def bench_step(name, preset, B, ctx, layers, iters, dev):
     return us
 
 
+SAMPLING = dict(temperature=0.8, top_k=50, top_p=0.95)
+
+
+def bench_tokens(name, preset, B, ctx, layers, iters, dev, samplers, graph):
+    cfg = get_preset(preset, n_layers=layers, seq_len=ctx)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    with torch.device(dev):
+        model = Transformer(cfg)
+    torch.set_default_dtype(prev)
+    model.eval()
+    model.flatten_(shadows=False)
+    cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev)
+    for k, v in zip(cache.k, cache.v):
+        k.normal_()
+        v.normal_()
+    warmup = 8
+    total = warmup + iters
+    start = ctx - total - 2  # the timed tokens end on a nearly full cache and never fill it
+    lens = torch.full((B,), start, dtype=torch.long, device=dev)
+    room = torch.full((B,), ctx, dtype=torch.long, device=dev)
+    tok0 = torch.randint(0, cfg.vocab_size, (B,), device=dev)
+    results = {}
+
+    def fresh_logits():
+        cache.kv_len.fill_(start)
+        return inf.decode_step(model, tok0, cache)
+
+    if "torch" in samplers:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(0)
+        st = {"logits": fresh_logits(), "done": torch.zeros(B, dtype=torch.bool, device=dev),
+              "out": torch.full((B, total), -1, dtype=torch.long, device=dev),
+              "count": torch.zeros(B, dtype=torch.long, device=dev), "i": 0}
+
+        def step_torch(_):  # the statements of generate()'s default loop
+            i = st["i"]
+            tok = inf.sample_token(st["logits"], generator=gen, **SAMPLING)
+            st["out"][:, i] = torch.where(st["done"], st["out"][:, i], tok)
+            st["count"] += (~st["done"]).long()
+            st["done"] = st["done"] | (room <= i)
+            tok = torch.where(st["done"], torch.zeros_like(tok), tok)
+            st["logits"] = inf.decode_step(model, tok, cache)
+            st["i"] = i + 1
+
+        results["eager + torch"] = timed_us(step_torch, iters, warmup)
+    if "philox" in samplers:
+        ds = inf.DeviceSampler(lens, room, total, seed=0, **SAMPLING)
+        st2 = {"logits": fresh_logits()}
+
+        def step_philox(_):
+            st2["logits"] = inf.decode_step(model, ds.sample(st2["logits"]), cache)
+
+        results["eager + philox"] = timed_us(step_philox, iters, warmup)
+    if graph:
+        ds = inf.DeviceSampler(lens, room, total, seed=0, **SAMPLING)
+        dg = inf.DecodeGraph(model, cache, fresh_logits(), ds)
+        results["graph + philox"] = timed_us(lambda _: dg.step(), iters, warmup)
+        assert dg.captured
+    print(f"{name}: one generated token (sample + bookkeeping + decode_step), {layers} layers, B={B} ctx={ctx}, "
+          f"V={cfg.vocab_size}")
+    base = results.get("eager + torch")
+    for arm, us in results.items():
+        rel = f"  ({base / us:.2f}x of eager + torch)" if base and arm != "eager + torch" else ""
+        print(f"  {arm:15s} {us:9.1f} us per token, {us / layers:7.1f} us per layer{rel}")
+    return results
+
+
+def bench_sampler(iters, dev):
+    C = _ext.native()
+    print("sampler alone, bf16 logits, T 0.8: us per call")
+    print(f"  {'V':>7s} {'B':>3s} {'setting':>10s} {'input':>9s} {'sample_':>9s} {'torch':>9s}")
+    for V in (32000, 128256):
+        for B in (1, 16):
+            pos = torch.arange(B, device=dev, dtype=torch.int32)
+            tok = torch.empty(B, dtype=torch.long, device=dev)
+            ws = torch.empty(C.sample_ws_bytes(B) // 4, dtype=torch.int32, device=dev)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(0)
+            inputs = [("normal", (torch.randn(B, V, device=dev) * 3).bfloat16()),
+                      ("all-equal", torch.full((B, V), 1.5, device=dev).bfloat16())]
+            for setting, k, p in (("top-k 50", 50, 1.0), ("top-p 0.95", 0, 0.95)):
+                for kind, x in inputs:
+                    hip = timed_us(lambda i: C.sample_(x, tok, 0.8, k, p, 0, pos=pos, ws=ws), iters)
+                    tor = timed_us(lambda i: inf.sample_token(x, 0.8, k, p, gen), max(5, iters // 5), 2)
+                    print(f"  {V:7d} {B:3d} {setting:>10s} {kind:>9s} {hip:9.1f} {tor:9.1f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4, help="layers of the model the decode_step timing builds")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--skip-step", action="store_true")
     ap.add_argument("--shapes", default="7b,llama3-8b", help="comma list of: 7b, llama3-8b")
+    ap.add_argument("--sampler", choices=("torch", "philox", "both"), default=None,
+                    help="time whole generated tokens with this sampler instead of the kernel / step tables")
+    ap.add_argument("--graph", action="store_true", help="add the hipGraph-replayed philox arm (DecodeGraph)")
+    ap.add_argument("--sample-bench", action="store_true", help="time the sampler alone")
     a = ap.parse_args()
     shapes = [s for s in SHAPES if s[0] in a.shapes.split(",")]
     dev = torch.device("cuda", 0)
     _ext.native()
+    if a.sample_bench:
+        bench_sampler(a.iters, dev)
+        return
+    if a.sampler or a.graph:
+        samplers = ("torch", "philox") if a.sampler == "both" else (a.sampler,) if a.sampler else ()
+        for name, preset, B, ctx in shapes:
+            bench_tokens(name, preset, B, ctx, a.layers, a.iters, dev, samplers, a.graph)
+        return
     for name, preset, B, ctx in shapes:
         bench_attention(name, get_preset(preset), B, ctx, a.iters, dev)
     if not a.skip_step:
