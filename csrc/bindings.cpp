@@ -660,49 +660,62 @@ int device_cus(const at::Tensor& t) {
   return cus;
 }
 
-// out [M, N] (+)= a^T b with a [K, M], b [K, N] (both row-major, K = tokens): the weight gradient
-// dW = dY^T X straight from the activations (no transposed copies), hand-written MFMA kernel.
-void wgrad_mm_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, bool accumulate) {
-  const Range range_("pyrecover::wgrad_mm");
+// What wgrad_mm_ and gemm_nt_ share. gemm_tensors: the operand checks that come before the op's own shape
+// check. gemm_args: the dtype / dimension / stride checks, and the argument block with the three operands
+// filled in. gemm_scratch: the split tail's fp32 partial tiles and tickets, sized by the plan the launcher
+// runs (gemm_plan.h), from the caching allocator (graph-capture safe); none when the tiles fill whole rounds.
+static void gemm_tensors(const at::Tensor& a, const at::Tensor& b, const at::Tensor& out) {
   check_dev(a, "a");
   check_row_major(a, "a");
   check_row_major(b, "b");
   check_row_major(out, "out");
   same_dev(a, b, "b");
   same_dev(a, out, "out");
-  const int64_t K = a.size(0), M = a.size(1), N = b.size(1);
-  TORCH_CHECK(b.size(0) == K && out.size(0) == M && out.size(1) == N, "wgrad_mm: shapes [K,M] x [K,N] -> [M,N]");
-  TORCH_CHECK(a.scalar_type() == b.scalar_type() && a.scalar_type() == out.scalar_type() && a.element_size() == 2,
-              "wgrad_mm: bf16/fp16 operands of one dtype");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 32 == 0 && K > 0, "wgrad_mm: M, N % 256 and K % 32");
-  TORCH_CHECK(a.stride(0) % 8 == 0 && b.stride(0) % 8 == 0 && out.stride(0) % 8 == 0, "wgrad_mm: 16-B rows");
-  const c10::DeviceGuard guard(a.device());
-  // scratch of the split tail (fp32 partial tiles + tickets), sized exactly for the launcher's
-  // split choice, from the caching allocator (graph-capture safe); none when tiles fill whole rounds
-  const int cus = device_cus(a);
-  const long nws = pra_wgrad_ws_floats((int)M, (int)N, (int)K, cus);
+}
+static pra_gemm_args gemm_args(const char* op, const at::Tensor& a, const at::Tensor& b, const at::Tensor& out,
+                               int64_t M, int64_t N, int64_t K) {
+  TORCH_CHECK(a.scalar_type() == b.scalar_type() && a.scalar_type() == out.scalar_type() && a.element_size() == 2, op,
+              ": bf16/fp16 operands of one dtype");
+  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 32 == 0 && K > 0, op, ": M, N % 256 and K % 32");
+  TORCH_CHECK(a.stride(0) % 8 == 0 && b.stride(0) % 8 == 0 && out.stride(0) % 8 == 0, op, ": 16-B rows");
+  pra_gemm_args g = {};
+  g.dtype = dt(a);
+  g.M = (int)M, g.N = (int)N, g.K = (int)K;
+  g.a = a.data_ptr(), g.lda = a.stride(0);
+  g.b = b.data_ptr(), g.ldb = b.stride(0);
+  g.c = out.data_ptr(), g.ldc = out.stride(0);
+  return g;
+}
+struct GemmScratch {
   at::Tensor ws, tickets;
+};
+static GemmScratch gemm_scratch(int kind, pra_gemm_args& g, const at::Tensor& a) {
+  GemmScratch sc;
+  g.cus = device_cus(a);
+  long nws = 0;
+  int ntk = 0;
+  pra_gemm_scratch(kind, g.M, g.N, g.K, g.cus, &nws, &ntk);
   if (nws > 0) {
-    ws = at::empty({(int64_t)nws}, a.options().dtype(at::kFloat));
-    tickets = at::empty({(int64_t)pra_wgrad_ticket_count((int)M, (int)N, (int)K, cus)}, a.options().dtype(at::kInt));
+    sc.ws = at::empty({(int64_t)nws}, a.options().dtype(at::kFloat));
+    sc.tickets = at::empty({(int64_t)ntk}, a.options().dtype(at::kInt));
+    g.ws = sc.ws.data_ptr<float>();
+    g.tickets = sc.tickets.data_ptr<int>();
   }
-  check(pra_wgrad_gemm(dt(a), a.data_ptr(), b.data_ptr(), out.data_ptr(), (int)M, (int)N, (int)K, a.stride(0),
-                       b.stride(0), out.stride(0), accumulate ? 1 : 0, ws.defined() ? ws.data_ptr<float>() : nullptr,
-                       tickets.defined() ? tickets.data_ptr<int>() : nullptr, cus, stream_of(a)),
-        "wgrad_mm");
+  return sc;
 }
 
-// timing experiments of the weight-gradient kernel (results are garbage; tools/gemm_exp.py)
-void wgrad_mm_exp_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t exp) {
-  check_dev(a, "a");
-  TORCH_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
-              "wgrad_mm_exp: bf16");
+// out [M, N] (+)= a^T b with a [K, M], b [K, N] (both row-major, K = tokens): the weight gradient
+// dW = dY^T X straight from the activations (no transposed copies), hand-written MFMA kernel.
+void wgrad_mm_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, bool accumulate) {
+  const Range range_("pyrecover::wgrad_mm");
+  gemm_tensors(a, b, out);
   const int64_t K = a.size(0), M = a.size(1), N = b.size(1);
-  TORCH_CHECK(b.size(0) == K && out.size(0) == M && out.size(1) == N, "wgrad_mm_exp: shapes");
+  TORCH_CHECK(b.size(0) == K && out.size(0) == M && out.size(1) == N, "wgrad_mm: shapes [K,M] x [K,N] -> [M,N]");
+  pra_gemm_args g = gemm_args("wgrad_mm", a, b, out, M, N, K);
+  g.accumulate = accumulate ? 1 : 0;
   const c10::DeviceGuard guard(a.device());
-  check(pra_wgrad_gemm_exp(a.data_ptr(), b.data_ptr(), out.data_ptr(), (int)M, (int)N, (int)K, a.stride(0), b.stride(0),
-                           out.stride(0), (int)exp, stream_of(a)),
-        "wgrad_mm_exp");
+  const GemmScratch sc = gemm_scratch(pra::kGemmWgrad, g, a);
+  check(pra_wgrad_gemm(&g, stream_of(a)), "wgrad_mm");
 }
 
 // NT GEMM with a fused epilogue (gemm_nt.hip): a [M, K], b [N, K] row-major (K-contiguous).
@@ -715,31 +728,21 @@ void gemm_nt_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t 
               const c10::optional<at::Tensor>& out2, const c10::optional<at::Tensor>& tab, int64_t S, int64_t D,
               int64_t nrot) {
   const Range range_("pyrecover::gemm_nt");
-  check_dev(a, "a");
-  check_row_major(a, "a");
-  check_row_major(b, "b");
-  check_row_major(out, "out");
-  same_dev(a, b, "b");
-  same_dev(a, out, "out");
+  gemm_tensors(a, b, out);
   const int64_t M = a.size(0), K = a.size(1), N = b.size(0);
   TORCH_CHECK(b.size(1) == K, "gemm_nt: a [M, K] and b [N, K]");
-  TORCH_CHECK(a.scalar_type() == b.scalar_type() && a.scalar_type() == out.scalar_type() && a.element_size() == 2,
-              "gemm_nt: bf16/fp16 operands of one dtype");
-  TORCH_CHECK(M % 256 == 0 && N % 256 == 0 && K % 32 == 0 && K > 0, "gemm_nt: M, N % 256 and K % 32");
-  TORCH_CHECK(a.stride(0) % 8 == 0 && b.stride(0) % 8 == 0 && out.stride(0) % 8 == 0, "gemm_nt: 16-B rows");
+  pra_gemm_args g = gemm_args("gemm_nt", a, b, out, M, N, K);
   TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(b.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
               "gemm_nt: 16-B aligned operands (the epilogue stores 16 B per lane)");
   TORCH_CHECK(epi >= 0 && epi <= 3, "gemm_nt: epi in 0..3");
-  int64_t F = 0;
-  void* c2 = nullptr;
-  int64_t ldc2 = 0;
-  const void* tabp = nullptr;
+  g.epi = (int)epi;
+  g.S = (int)S, g.D = (int)D, g.nrot = (int)nrot;
   if (epi == 0 || epi == 3) {
     TORCH_CHECK(out.size(0) == M && out.size(1) == N, "gemm_nt: out [M, N]");
   }
   if (epi == 1) {
-    F = N / 2;
+    const int64_t F = N / 2;
     TORCH_CHECK(N % 2 == 0 && F % 128 == 0, "gemm_nt swiglu: b = W1|W3 [2F, K], F % 128");
     TORCH_CHECK(out.size(0) == M && out.size(1) == N, "gemm_nt swiglu: gu [M, 2F]");
     TORCH_CHECK(out2.has_value(), "gemm_nt swiglu: needs out2 = a [M, F]");
@@ -749,12 +752,13 @@ void gemm_nt_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t 
                     out2->stride(0) % 8 == 0,
                 "gemm_nt swiglu: a [M, F]");
     TORCH_CHECK(reinterpret_cast<uintptr_t>(out2->data_ptr()) % 16 == 0, "gemm_nt swiglu: 16-B aligned out2");
-    c2 = out2->data_ptr();
-    ldc2 = out2->stride(0);
+    g.F = (int)F;
+    g.c2 = out2->data_ptr();
+    g.ldc2 = out2->stride(0);
   }
   if (epi == 2) {
-    F = N;
-    TORCH_CHECK(out.size(0) == M && out.size(1) == 2 * F, "gemm_nt swiglu bwd: gu [M, 2F] with b [F, K]");
+    g.F = (int)N;
+    TORCH_CHECK(out.size(0) == M && out.size(1) == 2 * N, "gemm_nt swiglu bwd: gu [M, 2F] with b [F, K]");
   }
   if (epi == 3) {
     TORCH_CHECK(tab.has_value(), "gemm_nt rope: needs tab");
@@ -763,22 +767,11 @@ void gemm_nt_(const at::Tensor& a, const at::Tensor& b, at::Tensor out, int64_t 
                 "gemm_nt rope: tab float32 [>= S, D/2, 2]");
     TORCH_CHECK(S > 0 && D > 0 && D % 8 == 0 && nrot % D == 0 && nrot <= N && M % S == 0,
                 "gemm_nt rope: S, D % 8, nrot % D, tokens % S");
-    tabp = tab->data_ptr();
+    g.tab = tab->data_ptr();
   }
   const c10::DeviceGuard guard(a.device());
-  const int cus = device_cus(a);
-  const long nws = pra_gemm_nt_ws_floats((int)M, (int)N, (int)K, cus);
-  at::Tensor ws, tickets;
-  // split tail scratch (exactly R * S partial tiles) and the tickets / tile counters, from the
-  // caching allocator (graph-safe)
-  if (nws > 0) ws = at::empty({(int64_t)nws}, a.options().dtype(at::kFloat));
-  const int ntk = pra_gemm_nt_ticket_count((int)M, (int)N, (int)K, cus);
-  if (ntk > 0) tickets = at::empty({(int64_t)ntk}, a.options().dtype(at::kInt));
-  check(pra_gemm_nt(dt(a), (int)epi, a.data_ptr(), b.data_ptr(), out.data_ptr(), (int)M, (int)N, (int)K, a.stride(0),
-                    b.stride(0), out.stride(0), c2, ldc2, (int)F, tabp, (int)S, (int)D, (int)nrot,
-                    ws.defined() ? ws.data_ptr<float>() : nullptr, tickets.defined() ? tickets.data_ptr<int>() : nullptr,
-                    cus, stream_of(a)),
-        "gemm_nt");
+  const GemmScratch sc = gemm_scratch(pra::kGemmNT, g, a);
+  check(pra_gemm_nt(&g, stream_of(a)), "gemm_nt");
 }
 
 // returns fp32 [2] = {norm, clip_coef}
@@ -1221,7 +1214,6 @@ PYBIND11_MODULE(_C, m) {
         py::arg("b2"));
   m.def("checksum", &checksum);
   m.def("wgrad_mm_", &wgrad_mm_);
-  m.def("wgrad_mm_exp_", &wgrad_mm_exp_);
   m.def("gemm_nt_", &gemm_nt_, py::arg("a"), py::arg("b"), py::arg("out"), py::arg("epi") = 0,
         py::arg("out2") = py::none(), py::arg("tab") = py::none(), py::arg("S") = 0, py::arg("D") = 0,
         py::arg("nrot") = 0);

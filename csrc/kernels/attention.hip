@@ -32,16 +32,11 @@
 #include "common.h"
 #include "attn_launch.h"
 
-// Variant switches (tools/attn_variants.sh builds the standalone harness per setting)
-#ifndef PRA_FWD_MINBLK
-#define PRA_FWD_MINBLK 2
-#endif
-#ifndef PRA_FWD_PRESCALE
-#define PRA_FWD_PRESCALE 0
-#endif
-#ifndef PRA_DQ_PRESCALE
-#define PRA_DQ_PRESCALE 0
-#endif
+// Variants that were built and lost; their code is in the history:
+//   forward with Q pre-multiplied by scale * log2(e) and score accumulators that start at -m (one v_exp
+//     per score, no FMA; register spills): measured slower: profiles/r5/attn/harness_base_vs_fwd_prescale.log
+//   the same for the pipelined dQ kernel (accumulators from -lse log2(e) / -delta; register spills, no log kept)
+//   fwd_p_kernel with a minimum of 1 block per CU instead of 2 in its launch bounds (no log kept)
 
 namespace pra {
 namespace attn {
@@ -227,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, 2) void fwd_kernel(const T* __restrict__ Q
 // wave's only diagonal tile is its last one.
 // ======================================================================================
 template <typename T, int D, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T* __restrict__ Q, const T* __restrict__ K,
+__global__ __launch_bounds__(NW * 64, 2) void fwd_p_kernel(const T* __restrict__ Q, const T* __restrict__ K,
                                                            const T* __restrict__ V, T* __restrict__ O,
                                                            float* __restrict__ LSE, int S, int Hq, int Hkv, long ldq,
                                                            long ldk, long ldv, long ldo, float scale_log2, float thr,
@@ -262,13 +257,6 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     qf[ks] = qrow < S ? *reinterpret_cast<const V8<T>*>(Qb + (long)qrow * ldq + 16 * ks + 8 * h2) : V8<T>{};
-#if PRA_FWD_PRESCALE
-    // Q pre-multiplied by scale * log2(e) (rounded to T: ~2^-9 relative per element, ~0.1% on P at
-    // D = 128), so the scores come out of the MFMA in log2 units, already minus the running max
-    // (the accumulator starts at -m: negm below): the softmax needs one v_exp per score, no FMA
-#pragma unroll
-    for (int j = 0; j < 8; ++j) qf[ks][j] = (T)((float)qf[ks][j] * scale_log2);
-#endif
   }
 
   f32x16 o[NDB];
@@ -305,10 +293,8 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, fmaxf(s0[r], s1[r]));
-    return PRA_FWD_PRESCALE ? half_max(mx) : half_max(mx) * scale_log2;
+    return half_max(mx) * scale_log2;
   };
-  f32x16 negm;  // -m_i in every register: the initial accumulator of a score tile (PRA_FWD_PRESCALE)
-
   f32x16 c0 = f32x16{}, c1 = f32x16{};  // scores of the tile being finished (two 32-key halves)
   if (lastw >= 0) {
     const T* Kt = slot(0);
@@ -319,16 +305,7 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
     }
     if (CAUSAL && lastw == 0) mask(c0, c1, 0);
     m_i = rowmax(c0, c1);
-#if PRA_FWD_PRESCALE
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      c0[r] -= m_i;
-      c1[r] -= m_i;
-    }
-#endif
   }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) negm[r] = -m_i;
 
   // the ring slot of tile t is a compile-time constant (loop unrolled by 3), so every LDS operand
   // address is a lane-constant base plus an immediate offset
@@ -354,22 +331,9 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
         constexpr int RA = NKS, EA = NEA / RA;  // phase A: regions / softmax elements per region
         constexpr int RB = 2 * NDB, EB = 32 / RB;
         constexpr int EBX = (32 - NEA) / (RB / 2);  // phase B exponentials per region
-#if PRA_FWD_PRESCALE
-        f32x16 n0 = negm, n1 = negm;
-#else
         f32x16 n0 = f32x16{}, n1 = f32x16{};
-#endif
         float rs = 0.f, mx = -INFINITY;
         auto expo = [&](int e) {  // element e of the 32 scores of tile t
-#if PRA_FWD_PRESCALE
-          if (e < 16) {
-            c0[e] = fexp2(c0[e]);
-            rs += c0[e];
-          } else {
-            c1[e - 16] = fexp2(c1[e - 16]);
-            rs += c1[e - 16];
-          }
-#else
           if (e < 16) {
             c0[e] = fexp2(fmaf(c0[e], scale_log2, -m_i));
             rs += c0[e];
@@ -377,7 +341,6 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
             c1[e - 16] = fexp2(fmaf(c1[e - 16], scale_log2, -m_i));
             rs += c1[e - 16];
           }
-#endif
         };
         // phase A: S(t+1) | exp, row sum of tile t
         V8<T> a0 = lo.rowk(Kn, 0, 0), a1 = lo.rowk(Kn, 32, 0);
@@ -433,23 +396,6 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
           __builtin_amdgcn_sched_barrier(0);
         }
         if (NEXT) {
-#if PRA_FWD_PRESCALE
-          mx = half_max(mx);  // max growth over m_i (the scores are relative to it)
-          if (!__all(mx <= thr)) {  // deferred rescale (tile t's P.V is already in O)
-            const float dlt = fmaxf(mx, 0.f);
-            const float alpha = fexp2(-dlt);
-            l_i *= alpha;
-#pragma unroll
-            for (int i = 0; i < NDB; ++i) o[i] *= alpha;
-            m_i += dlt;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              n0[r] -= dlt;
-              n1[r] -= dlt;
-              negm[r] = -m_i;
-            }
-          }
-#else
           mx = half_max(mx) * scale_log2;
           if (!__all(mx <= m_i + thr)) {  // deferred rescale (tile t's P.V is already in O)
             const float m_new = fmaxf(m_i, mx);
@@ -459,7 +405,6 @@ __global__ __launch_bounds__(NW * 64, PRA_FWD_MINBLK) void fwd_p_kernel(const T*
             for (int i = 0; i < NDB; ++i) o[i] *= alpha;
             m_i = m_new;
           }
-#endif
           c0 = n0;
           c1 = n1;
         }
@@ -1137,16 +1082,6 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dq_kernel(
       }
     }
     dl = half_sum(part);  // all 64 lanes (permlane32 swap)
-#if PRA_DQ_PRESCALE
-    // PIPE path: Q pre-multiplied by scale log2(e) (as the forward's PRA_FWD_PRESCALE), and the S / dP
-    // accumulators start at -lse log2(e) / -delta, so p = exp2(S') and dS = p dP' need no FMA / sub
-    if (PIPE) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[ks][j] = (T)((float)qf[ks][j] * scale_log2);
-    }
-#endif
     if (qrow < S && h2 == 0) {
       const long i = ((long)b * Hq + hq) * S + qrow;
       Delta[i] = dl;
@@ -1188,23 +1123,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dq_kernel(
         constexpr int R1 = NKS, R3 = NDB, NR = 2 * R1 + 2 * R3;
         constexpr int EA = 16 / R1, EB = 16 / R3;
         const int lim = qrow - k0 - 4 * h2;
-#if PRA_DQ_PRESCALE == 1
-        f32x16 s0, s1, p0, p1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] = -lse2;
-          p0[r] = -dl;
-        }
-        s1 = s0;
-        p1 = p0;
-#elif PRA_DQ_PRESCALE == 2  // S chains only (16 registers of constants instead of 32)
-        f32x16 s0, s1, p0 = f32x16{}, p1 = f32x16{};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s0[r] = -lse2;
-        s1 = s0;
-#else
         f32x16 s0 = f32x16{}, s1 = f32x16{}, p0 = f32x16{}, p1 = f32x16{};
-#endif
         V8<T> g0[2], g1[2];
         auto fetch = [&](int k, V8<T> (&o)[4]) {
           if (k < 2 * R1) {
@@ -1219,19 +1138,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void bwd_dq_kernel(
           }
         };
         auto soft = [&](f32x16& sv, f32x16& dp, int kb, int r) {
-#if PRA_DQ_PRESCALE == 1
-          float p = fexp2(sv[r]);
-          if (MASK && crow(r, 0) > lim - 32 * kb) p = 0.f;
-          dp[r] = p * dp[r];
-#elif PRA_DQ_PRESCALE == 2
-          float p = fexp2(sv[r]);
-          if (MASK && crow(r, 0) > lim - 32 * kb) p = 0.f;
-          dp[r] = p * (dp[r] - dl);
-#else
           float p = fexp2(fmaf(sv[r], scale_log2, -lse2));
           if (MASK && crow(r, 0) > lim - 32 * kb) p = 0.f;
           dp[r] = p * (dp[r] - dl);
-#endif
         };
         V8<T> cur[4], nxt[4];
         fetch(0, cur);

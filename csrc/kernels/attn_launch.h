@@ -5,8 +5,6 @@
 #include "common.h"
 #include "launchers.h"
 
-#include <type_traits>
-
 namespace pra {
 namespace attn {
 
@@ -38,27 +36,11 @@ inline hipError_t dispatch_16bit(int dtype, F&& f) {
   return hipErrorInvalidValue;
 }
 
-// A runtime value that is one of Vs. dispatch(f, One<..>{x}, One<..>{y}, ...) calls
-// f(integral_constant<int, x>{}, integral_constant<int, y>{}, ...), so each kernel's launch is written
-// once, with the arguments' values (d(), c(), ...) as template arguments; false when a value is not in
-// its list (the shape checks run first). The lists ascend: instantiations then come out in the order
-// the kernels have always had in the code object (D 128 before 64, causal before full, 8 waves before 4).
-template <int... Vs>
-struct One {
-  int v;
-};
+// The value lists of dispatch (common.h). They ascend: instantiations then come out in the order the
+// kernels have always had in the code object (D 128 before 64, causal before full, 8 waves before 4).
 using HeadDim = One<64, 128>;
 using Causal = One<0, 1>;
 using Waves = One<4, 8>;  // BwdPlan::nw
-template <class F>
-inline bool dispatch(F&& f) {
-  f();
-  return true;
-}
-template <class F, int... Vs, class... Rest>
-inline bool dispatch(F&& f, One<Vs...> s, Rest... rest) {
-  return ((s.v == Vs && dispatch([&](auto... ic) { f(std::integral_constant<int, Vs>{}, ic...); }, rest...)) || ...);
-}
 
 }  // namespace attn
 }  // namespace pra

@@ -11,6 +11,8 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace pra {
 
 enum DType : int { kF32 = 0, kBF16 = 1, kF16 = 2 };
@@ -134,6 +136,25 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
   for (int i = 0; i < NW; ++i) r = fmaxf(r, scratch[i]);
   __syncthreads();
   return r;
+}
+
+// ---- host side: runtime value -> template argument ---------------------------------------
+// A runtime value that is one of Vs. dispatch(f, One<..>{x}, One<..>{y}, ...) calls
+// f(integral_constant<int, x>{}, integral_constant<int, y>{}, ...), so each kernel's launch is written
+// once, with the arguments' values (d(), c(), ...) as template arguments; false when a value is not in
+// its list (the shape checks run first).
+template <int... Vs>
+struct One {
+  int v;
+};
+template <class F>
+inline bool dispatch(F&& f) {
+  f();
+  return true;
+}
+template <class F, int... Vs, class... Rest>
+inline bool dispatch(F&& f, One<Vs...> s, Rest... rest) {
+  return ((s.v == Vs && dispatch([&](auto... ic) { f(std::integral_constant<int, Vs>{}, ic...); }, rest...)) || ...);
 }
 
 }  // namespace pra

@@ -8,8 +8,8 @@
 // K-slow operands through ds_read_b64_tr_b16, the NT kernel K-contiguous ones with ds_read_b128.
 #pragma once
 #include "common.h"
-
-#include <type_traits>
+#include "gemm_plan.h"
+#include "launchers.h"
 
 namespace pra {
 namespace gm {
@@ -24,17 +24,7 @@ using V8 = typename Elem<T>::v8;
 template <int N>
 using IC = std::integral_constant<int, N>;
 
-// f(IC<I>{}) for I in [I0, N): a compile-time loop (a 128-step #pragma unroll body with nested loops
-// can stay rolled, which turns register arrays into scratch)
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-constexpr int BM = 256, BN = 256, BK = 32, NTH = 256, NS = 5;
+constexpr int BM = kGemmTile, BN = kGemmTile, BK = 32, NTH = 256, NS = 5;
 constexpr int TILE = BK * 256;              // elements per staged operand tile (16 KiB)
 constexpr int NI = TILE * 2 / (NTH * 16);   // LDS-DMA instructions per lane per operand tile (4)
 constexpr int GM = 8;                       // M-tiles per group of the tile order
@@ -63,15 +53,9 @@ __device__ __forceinline__ void dma16s_go(const void* sbase, uint32_t voff) {
 // s_waitcnt vmcnt(N) for a compile-time N
 template <int N>
 __device__ __forceinline__ void wait_vm() {
-  static_assert(N == 0 || N == 8 || N == 15 || N == 16 || N == 18 || N == 24 || N == 32 || N == 48, "add the count");
-  if constexpr (N == 48) asm volatile("s_waitcnt vmcnt(48)" ::: "memory");
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (N == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-  if constexpr (N == 18) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-  if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+  static_assert(N == 16 || N == 24, "add the count");
   if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   if constexpr (N == 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-  if constexpr (N == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
 }
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
@@ -97,21 +81,36 @@ __device__ __forceinline__ void tile_origin(int lin, int tiles_m, int tiles_n, l
   n0 = (long)((lin % (GM * tiles_n)) / gsz) * BN;
 }
 
-}  // namespace gm
-
-// Split of the partial last round (host side, shared by the GEMM launchers): the R = nwg % cus
-// tail tiles are split S ways over K when that fills whole rounds better (S <= smax, ties -> the
-// smaller S). Returns S (1 = unsplit).
-inline int gemm_tail_split(int nwg, int cus, int nk, int smax) {
-  if (nwg <= cus || nwg % cus == 0) return 1;
-  const int R = nwg % cus;
-  double best = 1.0;  // unsplit: one more round
-  int S = 1;
-  for (int c = 2; c <= smax && c <= 8 && c <= nk; ++c) {
-    const double t = (double)((R * c + cus - 1) / cus) / c;
-    if (t < best - 1e-9) best = t, S = c;
-  }
-  return S;
+// Zeroes the split tail's tickets. A kernel, not hipMemsetAsync: replayed from a captured HIP graph
+// (train.py --compile), the memset node's zeros were not seen by the GEMM's ticket atomics and most
+// split tiles were never reduced (tests/test_kernels_gpu.py, graph-capture test). A template so that
+// both GEMM translation units can hold it.
+template <int NT>
+__global__ __launch_bounds__(NT) void zero_i32_kernel(int* __restrict__ p, int n) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+inline void zero_tickets(int* tickets, int n, hipStream_t s) {
+  hipLaunchKernelGGL(zero_i32_kernel<256>, dim3((n + 255) / 256), dim3(256), 0, s, tickets, n);
 }
 
+// What both launchers check of a pra_gemm_args block, and the plan they run: the split tail only when
+// the caller handed both scratch buffers
+inline bool gemm_args_ok(const pra_gemm_args& a) {
+  return !(a.M % BM || a.N % BN || a.K % BK || a.K <= 0 || a.lda % 8 || a.ldb % 8 || a.ldc % 8 || a.cus <= 0);
+}
+inline GemmPlan gemm_launch_plan(int kind, const pra_gemm_args& a) {
+  const GemmPlan p = gemm_plan(kind, a.M, a.N, a.K, a.cus);
+  return a.ws && a.tickets ? p : gemm_unsplit(p);
+}
+
+// f(T{}) for the element type of `dtype`
+template <class F>
+inline hipError_t dispatch_elem(int dtype, F&& f) {
+  if (dtype == kBF16) return f(__bf16{});
+  if (dtype == kF16) return f(_Float16{});
+  return hipErrorInvalidValue;
+}
+
+}  // namespace gm
 }  // namespace pra

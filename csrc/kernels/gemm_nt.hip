@@ -19,7 +19,7 @@
 // address instead.
 //
 // Orientation: acc = mfma(B fragment, A fragment), so a lane holds one output row m and 4
-// consecutive columns n in its 4 registers: RoPE pairs (2i, 2i+1) are in one lane; with ST16 two
+// consecutive columns n in its 4 registers: RoPE pairs (2i, 2i+1) are in one lane; two
 // 16 x 16 blocks are paired through v_permlane16_swap so each lane writes 16 contiguous bytes.
 //
 // Epilogues (EPI):
@@ -85,66 +85,19 @@ __device__ unsigned long long* pra_nt_stamp_out;
   } while (0)
 #endif
 
-// SCHED 1 (hipBLASLt's chunk order, 4 barriers) vs 0 (3 phases, 2 barriers) and VOFF (per-DMA row
-// offsets in VGPRs) at 32768x4096x4096, three interleaved rounds: 3-phase 1438, 4-barrier 1445,
-// 4-barrier + VOFF 1449, 3-phase + VOFF 1454 TF (the VGPR offsets take ~50 cycles per chunk off
-// phase 2); hipBLASLt 1508-1580 on this shape (profiles/r4/gemm_nt_hipblaslt_order*.log)
-#ifndef PRA_NT_SCHED
-#define PRA_NT_SCHED 0
-#endif
-// ST16: epilogue stores of 16 B (v_permlane16_swap pairs two 16-column blocks) instead of 8 B: per
-// 256x256 tile 11.8k instead of 16.1k cycles from loop end to stores retired; 32768x11008x4096
-// 1434 -> 1466 TF (profiles/r4/gemm_nt_st16_epilogue.log)
-// (Persistent workgroups walking per-XCD tile ranges through atomic counters, with the next tile's
-// prologue DMAs issued before the current tile's epilogue stores, measured 0.2-1.1% slower:
-// profiles/r4/gemm_nt_persistent_ab.log.)
-#ifndef PRA_NT_EPI2_PIPE  // SwiGLU backward epilogue with row-block loads two blocks ahead (epi2_pipe)
-#define PRA_NT_EPI2_PIPE 1
-#endif
-#ifndef PRA_NT_EPI2_DEPTH  // row blocks of g / u in flight in epi2_pipe (32 VGPRs each)
-#define PRA_NT_EPI2_DEPTH 3
-#endif
-#ifndef PRA_NT_ST16
-#define PRA_NT_ST16 1
-#endif
-#ifndef PRA_NT_VOFF
-#define PRA_NT_VOFF 1
-#endif
-#ifndef PRA_NT_P1
-#define PRA_NT_P1 32
-#endif
-#ifndef PRA_NT_RS1
-#define PRA_NT_RS1 1
-#endif
-#ifndef PRA_NT_P3
-#define PRA_NT_P3 16
-#endif
-#ifndef PRA_NT_RS3
-#define PRA_NT_RS3 1
-#endif
-// M0SPLIT 1: 1432-1449 vs 1429-1431 TF without (32768x4096x4096; per-chunk phase 2 1467 vs 1515
-// cycles); spreading the fragment reads one per two or three MFMAs (RS > 1) was 2-9% slower:
-// profiles/r4/gemm_nt_schedule_variants*.log
-#ifndef PRA_NT_M0SPLIT
-#define PRA_NT_M0SPLIT 1
-#endif
-
-// PRA_NT_SCHED 1 event tables: the MFMA index after which DMA d (A rows 0..7, B rows 8..15) of
-// chunk t + 2 issues, and after which fragment read 8 g + r issues (g: 0 fb1, 1 fa1 of chunk t;
-// 2 fb0, 3 fa0 of chunk t + 1)
-constexpr int kNt4Dma[16] = {61, 64, 85, 87, 89, 94, 98, 124, 22, 25, 28, 31, 34, 52, 55, 58};
-constexpr int kNt4Read[32] = {1,   3,   5,   7,   9,   11,  13,  15,  24, 27, 30, 33, 36, 38, 40, 42,
-                              69,  71,  73,  75,  77,  79,  81,  83,  106, 108, 110, 112, 114, 116, 118, 120};
-constexpr int nt4_dma_at(int q) {
-  for (int d = 0; d < 16; ++d)
-    if (kNt4Dma[d] == q) return d;
-  return -1;
-}
-constexpr int nt4_read_at(int q) {
-  for (int i = 0; i < 32; ++i)
-    if (kNt4Read[i] == q) return i;
-  return -1;
-}
+// Variants that were measured and lost; their code is in the history, one line each here:
+//   hipBLASLt's 4-barrier chunk order (3-phase + VGPR offsets 1454 vs 1445-1449 TF at 32768x4096x4096):
+//     measured slower: profiles/r4/gemm_nt_hipblaslt_order*.log
+//   per-DMA row offsets folded into the SGPR base instead of 16 VGPRs (~50 cycles more per chunk in
+//     phase 2): measured slower: profiles/r4/gemm_nt_hipblaslt_order*.log
+//   8-byte epilogue stores (16.1k vs 11.8k cycles per tile from loop end to stores retired;
+//     32768x11008x4096 1434 vs 1466 TF): measured slower: profiles/r4/gemm_nt_st16_epilogue.log
+//   SwiGLU backward epilogue one row block at a time (675 us slower at 7B W2):
+//     measured slower: profiles/r4/gemm_nt_bench_swiglu_epilogues.log, profiles/r5/epi2/
+//   each DMA's M0 write next to its load (1429-1431 vs 1432-1449 TF), and fragment reads spread one per
+//     two or three MFMAs (2-9%): measured slower: profiles/r4/gemm_nt_schedule_variants*.log
+//   persistent workgroups walking per-XCD tile ranges through atomic counters, the next tile's prologue
+//     DMAs issued before the epilogue stores (0.2-1.1%): measured slower: profiles/r4/gemm_nt_persistent_ab.log
 
 // the XOR swizzle of the 16-B chunk of row r: g((r >> 2) & 3), g = {0, 2, 3, 1}
 __device__ __forceinline__ int swz(int r) {
@@ -227,7 +180,9 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
   // epilogue: lane holds row m0 + 128 wm + 16 i + (l & 15), columns n0 + 128 wn + 16 j + 4 (l >> 4) + 0..3
   const int l16 = lane & 15, g4 = lane >> 4;
 
-  // SwiGLU backward epilogue (EPI 2, ST16 layout) with the g / u loads of row block i + 2 in flight
+  // SwiGLU backward epilogue (EPI 2): dg = silu'(g) * round(da * u), du = round(da * round(silu(g)))
+  // in place over gu, 16-B accesses at the positions of the plain epilogue below (v_permlane16_swap is
+  // its own inverse on that pairing), with the g / u loads of row block i + 2 in flight
   // while block i is computed and stored. The one-block-at-a-time form waited a full load (and the
   // previous block's stores, which count in vmcnt) per row block: 8 serialized HBM round trips per
   // tile, and every CU reaches its epilogue at the same time (tiles run in lockstep rounds), so the
@@ -239,7 +194,7 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
     auto gptr = [&](int i) __attribute__((always_inline)) -> T* {
       return C + (m0 + 128 * wm + 16 * i + l16) * ldc + n0 + 128 * wn + 4 * g4 + so;
     };
-    constexpr int DEPTH = PRA_NT_EPI2_DEPTH;  // row blocks in flight
+    constexpr int DEPTH = 3;  // row blocks of g / u in flight (32 VGPRs each)
     uint4 gb[DEPTH][4], ub[DEPTH][4];
     auto load = [&](int i, uint4 (&g8)[4], uint4 (&u8)[4]) __attribute__((always_inline)) {
       const T* gp = gptr(i);
@@ -275,7 +230,7 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
         unpack4<T>(gw[j], g);
         unpack4<T>(uw[j], u);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {  // the math of the one-block form below, element for element
+        for (int e = 0; e < 4; ++e) {  // swiglu_bwd_kernel's math, element for element
           const float d = rnd16<T>(acc[i][j][e]);
           const float sg = 1.f / (1.f + __expf(-g[e]));
           const float a = rnd16<T>(g[e] * sg);
@@ -301,7 +256,7 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
   };
 
   auto store_c = [&](long m0, long n0) __attribute__((always_inline)) {
-    if constexpr (EPI == 2 && PRA_NT_ST16 && PRA_NT_EPI2_PIPE) {
+    if constexpr (EPI == 2) {
       epi2_pipe(m0, n0);
       return;
     }
@@ -309,7 +264,6 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
     for (int i = 0; i < 8; ++i) {
       const long row = m0 + 128 * wm + 16 * i + l16;
       if constexpr (EPI == 0 || EPI == 3) {
-        T* rowp = C + row * ldc + n0 + 128 * wn + 4 * g4;
         int pos = 0;
         if constexpr (EPI == 3) pos = (int)(row % ep.S);
         auto vals = [&](int j, float (&v)[4]) __attribute__((always_inline)) {
@@ -325,27 +279,18 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
             }
           }
         };
-        if constexpr (PRA_NT_ST16) {
-          // blocks j, j + 1 through v_permlane16_swap (lane rows g4 even <-> odd): lane row g4
-          // ends up with 8 consecutive columns, 16 (j + (g4 & 1)) + 8 (g4 >> 1) + 0..7, and stores
-          // them as one 16-B write (32 instead of 64 store instructions per lane)
-          T* sp = C + row * ldc + n0 + 128 * wn + 16 * (g4 & 1) + 8 * (g4 >> 1);
+        // blocks j, j + 1 through v_permlane16_swap (lane rows g4 even <-> odd): lane row g4
+        // ends up with 8 consecutive columns, 16 (j + (g4 & 1)) + 8 (g4 >> 1) + 0..7, and stores
+        // them as one 16-B write (32 instead of 64 store instructions per lane)
+        T* sp = C + row * ldc + n0 + 128 * wn + 16 * (g4 & 1) + 8 * (g4 >> 1);
 #pragma unroll
-          for (int j = 0; j < 8; j += 2) {
-            float va[4], vb[4];
-            vals(j, va);
-            vals(j + 1, vb);
-            const auto s0 = __builtin_amdgcn_permlane16_swap(pack_x2<T>(va[0], va[1]), pack_x2<T>(vb[0], vb[1]), false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(pack_x2<T>(va[2], va[3]), pack_x2<T>(vb[2], vb[3]), false, false);
-            *reinterpret_cast<uint4*>(sp + 16 * j) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float v[4];
-            vals(j, v);
-            *reinterpret_cast<uint2*>(rowp + 16 * j) = make_uint2(pack_x2<T>(v[0], v[1]), pack_x2<T>(v[2], v[3]));
-          }
+        for (int j = 0; j < 8; j += 2) {
+          float va[4], vb[4];
+          vals(j, va);
+          vals(j + 1, vb);
+          const auto s0 = __builtin_amdgcn_permlane16_swap(pack_x2<T>(va[0], va[1]), pack_x2<T>(vb[0], vb[1]), false, false);
+          const auto s1 = __builtin_amdgcn_permlane16_swap(pack_x2<T>(va[2], va[3]), pack_x2<T>(vb[2], vb[3]), false, false);
+          *reinterpret_cast<uint4*>(sp + 16 * j) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
         }
       } else if constexpr (EPI == 1) {
         // features f0 + 16 j + 4 g4 + 0..3 (j < 4): gate in acc[i][j], up in acc[i][j + 4]
@@ -365,91 +310,19 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
           o[2] = pack_x2<T>(u[0], u[1]); o[3] = pack_x2<T>(u[2], u[3]);
           o[4] = pack_x2<T>(a[0], a[1]); o[5] = pack_x2<T>(a[2], a[3]);
         };
-        if constexpr (PRA_NT_ST16) {  // as EPI 0: features 16 (j + (g4 & 1)) + 8 (g4 >> 1) + 0..7 per lane
-          const long s0 = (16 * (g4 & 1) + 8 * (g4 >> 1)) - 4 * g4;
+        // as EPI 0: features 16 (j + (g4 & 1)) + 8 (g4 >> 1) + 0..7 per lane
+        const long s0 = (16 * (g4 & 1) + 8 * (g4 >> 1)) - 4 * g4;
 #pragma unroll
-          for (int j = 0; j < 4; j += 2) {
-            uint32_t x[6], y[6];
-            gua(j, x);
-            gua(j + 1, y);
-            T* dst[3] = {gp + s0 + 16 * j, up + s0 + 16 * j, ap + s0 + 16 * j};
+        for (int j = 0; j < 4; j += 2) {
+          uint32_t x[6], y[6];
+          gua(j, x);
+          gua(j + 1, y);
+          T* dst[3] = {gp + s0 + 16 * j, up + s0 + 16 * j, ap + s0 + 16 * j};
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              const auto w0 = __builtin_amdgcn_permlane16_swap(x[2 * k], y[2 * k], false, false);
-              const auto w1 = __builtin_amdgcn_permlane16_swap(x[2 * k + 1], y[2 * k + 1], false, false);
-              *reinterpret_cast<uint4*>(dst[k]) = make_uint4(w0[0], w1[0], w0[1], w1[1]);
-            }
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            uint32_t x[6];
-            gua(j, x);
-            *reinterpret_cast<uint2*>(gp + 16 * j) = make_uint2(x[0], x[1]);
-            *reinterpret_cast<uint2*>(up + 16 * j) = make_uint2(x[2], x[3]);
-            *reinterpret_cast<uint2*>(ap + 16 * j) = make_uint2(x[4], x[5]);
-          }
-        }
-      } else {  // EPI == 2: dg = silu'(g) * round(da * u), du = round(da * round(silu(g))) in place over gu
-        T* gp = C + row * ldc + n0 + 128 * wn + 4 * g4;
-        T* up = gp + ep.F;
-        uint2 gw[8], uw[8];
-        if constexpr (PRA_NT_ST16) {
-          // 16-B loads at the ST16 positions, swapped back to this lane's own 4 columns of blocks
-          // j and j + 1 (v_permlane16_swap is its own inverse on this pairing)
-          const long so = (16 * (g4 & 1) + 8 * (g4 >> 1)) - 4 * g4;
-#pragma unroll
-          for (int j = 0; j < 8; j += 2) {
-            const uint4 g8 = *reinterpret_cast<const uint4*>(gp + so + 16 * j);
-            const uint4 u8 = *reinterpret_cast<const uint4*>(up + so + 16 * j);
-            const auto g0 = __builtin_amdgcn_permlane16_swap(g8.x, g8.z, false, false);
-            const auto g1 = __builtin_amdgcn_permlane16_swap(g8.y, g8.w, false, false);
-            const auto u0 = __builtin_amdgcn_permlane16_swap(u8.x, u8.z, false, false);
-            const auto u1 = __builtin_amdgcn_permlane16_swap(u8.y, u8.w, false, false);
-            gw[j] = make_uint2(g0[0], g1[0]);
-            gw[j + 1] = make_uint2(g0[1], g1[1]);
-            uw[j] = make_uint2(u0[0], u1[0]);
-            uw[j + 1] = make_uint2(u0[1], u1[1]);
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {  // all loads first: one wait for the whole row block
-            gw[j] = *reinterpret_cast<const uint2*>(gp + 16 * j);
-            uw[j] = *reinterpret_cast<const uint2*>(up + 16 * j);
-          }
-        }
-        uint2 ogw[8], ouw[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float g[4], u[4], og[4], ou[4];
-          unpack4<T>(gw[j], g);
-          unpack4<T>(uw[j], u);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float d = rnd16<T>(acc[i][j][e]);
-            const float sg = 1.f / (1.f + __expf(-g[e]));
-            const float a = rnd16<T>(g[e] * sg);
-            const float dd = rnd16<T>(d * u[e]);
-            ou[e] = d * a;
-            og[e] = dd * sg * (1.f + g[e] * (1.f - sg));
-          }
-          ogw[j] = make_uint2(pack_x2<T>(og[0], og[1]), pack_x2<T>(og[2], og[3]));
-          ouw[j] = make_uint2(pack_x2<T>(ou[0], ou[1]), pack_x2<T>(ou[2], ou[3]));
-          if constexpr (!PRA_NT_ST16) {
-            *reinterpret_cast<uint2*>(gp + 16 * j) = ogw[j];
-            *reinterpret_cast<uint2*>(up + 16 * j) = ouw[j];
-          }
-        }
-        if constexpr (PRA_NT_ST16) {
-          const long so = (16 * (g4 & 1) + 8 * (g4 >> 1)) - 4 * g4;
-#pragma unroll
-          for (int j = 0; j < 8; j += 2) {
-            const auto g0 = __builtin_amdgcn_permlane16_swap(ogw[j].x, ogw[j + 1].x, false, false);
-            const auto g1 = __builtin_amdgcn_permlane16_swap(ogw[j].y, ogw[j + 1].y, false, false);
-            const auto u0 = __builtin_amdgcn_permlane16_swap(ouw[j].x, ouw[j + 1].x, false, false);
-            const auto u1 = __builtin_amdgcn_permlane16_swap(ouw[j].y, ouw[j + 1].y, false, false);
-            *reinterpret_cast<uint4*>(gp + so + 16 * j) = make_uint4(g0[0], g1[0], g0[1], g1[1]);
-            *reinterpret_cast<uint4*>(up + so + 16 * j) = make_uint4(u0[0], u1[0], u0[1], u1[1]);
+          for (int k = 0; k < 3; ++k) {
+            const auto w0 = __builtin_amdgcn_permlane16_swap(x[2 * k], y[2 * k], false, false);
+            const auto w1 = __builtin_amdgcn_permlane16_swap(x[2 * k + 1], y[2 * k + 1], false, false);
+            *reinterpret_cast<uint4*>(dst[k]) = make_uint4(w0[0], w1[0], w0[1], w1[1]);
           }
         }
       }
@@ -500,8 +373,7 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // B rows first (d = 8..15, then 0..7): the 4-barrier schedule waits for a chunk's B half
-    // before its A half
+    // B rows first (d = 8..15, then 0..7): the first fragment reads after the wait are mostly B's
 #pragma unroll
     for (int e = 0; e < 16; ++e) dma(0, c0, (e + 8) & 15);
 #pragma unroll
@@ -523,34 +395,24 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
       else
         acc[i][j] = mfma16(fb1[j], fa1[i], acc[i][j]);
     };
-    // schedule knobs (defaults: the production schedule; tools/nt_stamps.hip builds variants):
-    // P1 / P3 MFMAs in phases 1 / 3, one fragment read per RS1 / RS3 MFMAs, phase 2 = the rest with
-    // the 16 DMAs spread evenly; M0SPLIT puts one MFMA between each DMA's M0 write and its load
-    constexpr int P1 = PRA_NT_P1, RS1 = PRA_NT_RS1, P3 = PRA_NT_P3, RS3 = PRA_NT_RS3;
+    // the schedule: P1 / P3 MFMAs in phases 1 / 3, each with 16 fragment reads, one per MFMA; phase 2 =
+    // the rest, MD MFMAs per DMA, one of them between the DMA's M0 write and its load
+    constexpr int P1 = 32, P3 = 16;
     constexpr int MD = (128 - P1 - P3) / 16;
-    static_assert(P1 >= 16 * RS1 && P3 >= 16 * RS3 && P3 <= 64 && (128 - P1 - P3) % 16 == 0 && MD >= 2,
-                  "NT schedule knobs");
+    static_assert(P1 >= 16 && P3 == 16 && (128 - P1 - P3) % 16 == 0 && MD >= 2, "NT schedule");
     auto dma_lds = [&](int b, int d) __attribute__((always_inline)) {
       return ldsw + (uint32_t)((b * 2 + (d >> 3)) * TILE64 * sizeof(T) + (d & 7) * 4 * 1024);
     };
-    // PRA_NT_VOFF: each DMA's row offset lives in a VGPR (16 loop-invariant registers), so the SGPR
-    // base only moves once per chunk and operand instead of once per DMA (hipBLASLt's form)
-    uint32_t vo[PRA_NT_VOFF ? 16 : 1];
-    if constexpr (PRA_NT_VOFF) {
+    // each DMA's row offset lives in a VGPR (16 loop-invariant registers), so the SGPR base only
+    // moves once per chunk and operand instead of once per DMA (hipBLASLt's form)
+    uint32_t vo[16];
 #pragma unroll
-      for (int d = 0; d < 16; ++d)
-        vo[d] = d >= 8 ? vob64 + (uint32_t)((long)row_b64(d & 7) * ldb * (long)sizeof(T))
-                       : voa64 + (uint32_t)((long)row_a64(d & 7) * lda * (long)sizeof(T));
-    }
+    for (int d = 0; d < 16; ++d)
+      vo[d] = d >= 8 ? vob64 + (uint32_t)((long)row_b64(d & 7) * ldb * (long)sizeof(T))
+                     : voa64 + (uint32_t)((long)row_a64(d & 7) * lda * (long)sizeof(T));
     auto dma_go = [&](int c, int d) __attribute__((always_inline)) {
       c = min(c, c1 - 1);
-      const int i = d & 7;
-      if constexpr (PRA_NT_VOFF)
-        dma16s_go((d >= 8 ? Bb : Ab) + (long)c * 64, vo[PRA_NT_VOFF ? d : 0]);
-      else if (d >= 8)
-        dma16s_go(Bb + (long)row_b64(i) * ldb + (long)c * 64, vob64);
-      else
-        dma16s_go(Ab + (long)row_a64(i) * lda + (long)c * 64, voa64);
+      dma16s_go((d >= 8 ? Bb : Ab) + (long)c * 64, vo[d]);
     };
     auto chunk = [&](auto b_c, int t) __attribute__((always_inline)) {
       constexpr int b = decltype(b_c)::value;
@@ -558,18 +420,17 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-#pragma unroll
-        for (int k = 0; k < RS1; ++k) mf(r * RS1 + k);
+        mf(r);
         if (r < 8)
           fb1[r] = fragB(b, 1, r);
         else
           fa1[r - 8] = fragA(b, 1, r - 8);
-        __builtin_amdgcn_sched_group_barrier(0x008, RS1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
 #pragma unroll
-      for (int q = 16 * RS1; q < P1; ++q) mf(q);
-      if constexpr (P1 > 16 * RS1) __builtin_amdgcn_sched_group_barrier(0x008, P1 - 16 * RS1, 0);
+      for (int q = 16; q < P1; ++q) mf(q);
+      if constexpr (P1 > 16) __builtin_amdgcn_sched_group_barrier(0x008, P1 - 16, 0);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), visible to the compiler's wait counting
       PRA_NT_STAMP(ts1);
@@ -579,19 +440,13 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
       // phase 2: MFMA P1..127-P3 with the 16 DMA instructions of chunk t + 2 into buffer b
 #pragma unroll
       for (int d = 0; d < 16; ++d) {
-        if constexpr (PRA_NT_M0SPLIT) {
-          m0_set(dma_lds(b, d));
-          __builtin_amdgcn_sched_barrier(0);
-          mf(P1 + MD * d);
-          __builtin_amdgcn_sched_barrier(0);
-          dma_go(t + 2, d);
+        m0_set(dma_lds(b, d));
+        __builtin_amdgcn_sched_barrier(0);
+        mf(P1 + MD * d);
+        __builtin_amdgcn_sched_barrier(0);
+        dma_go(t + 2, d);
 #pragma unroll
-          for (int k = 1; k < MD; ++k) mf(P1 + MD * d + k);
-        } else {
-          dma(b, t + 2, d);
-#pragma unroll
-          for (int k = 0; k < MD; ++k) mf(P1 + MD * d + k);
-        }
+        for (int k = 1; k < MD; ++k) mf(P1 + MD * d + k);
         __builtin_amdgcn_sched_barrier(0);
       }
       PRA_NT_STAMP(ts3);
@@ -609,87 +464,25 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
       // chunk t + 1 (buffer b ^ 1) in first-use order
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-#pragma unroll
-        for (int k = 0; k < RS3; ++k) mf(128 - P3 + r * RS3 + k);
+        mf(128 - P3 + r);
         if (r == 0)
           fa0[0] = fragA(b ^ 1, 0, 0);
         else if (r < 9)
           fb0[r - 1] = fragB(b ^ 1, 0, r - 1);
         else
           fa0[r - 8] = fragA(b ^ 1, 0, r - 8);
-        __builtin_amdgcn_sched_group_barrier(0x008, RS3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
-#pragma unroll
-      for (int q = 128 - P3 + 16 * RS3; q < 128; ++q) mf(q);
-      if constexpr (P3 > 16 * RS3) __builtin_amdgcn_sched_group_barrier(0x008, P3 - 16 * RS3, 0);
       __builtin_amdgcn_sched_barrier(0);
-    };
-    // PRA_NT_SCHED 1: hipBLASLt's 256x256x64 DTL/PGR2 chunk order (read off its gfx950 ISA), four
-    // barriers per chunk so every phase frees or publishes one operand half:
-    //   MFMA 0-19    B k-substep-1 reads of chunk t (1 per 2 MFMA); lgkmcnt(0) + barrier 1: B half free
-    //   MFMA 20-50   5 B DMAs of chunk t + 2, A k-substep-1 reads; lgkmcnt(0) + barrier 2: A half free
-    //   MFMA 51-67   3 B + 2 A DMAs; vmcnt(18) + barrier 3: chunk t + 1's B half landed
-    //   MFMA 68-104  B k-substep-0 reads of chunk t + 1 (fb0 is free after MFMA 63), 5 A DMAs;
-    //                vmcnt(15) + barrier 4: chunk t + 1 landed
-    //   MFMA 105-127 A k-substep-0 reads of chunk t + 1, the last A DMA
-    // Every DMA's M0 write sits one MFMA ahead of its load.
-    auto chunk4 = [&](auto b_c, int t) __attribute__((always_inline)) {
-      constexpr int b = decltype(b_c)::value;
-      __builtin_amdgcn_sched_barrier(0);
-      static_for<0, 128>([&](auto q_c) __attribute__((always_inline)) {
-        constexpr int q = decltype(q_c)::value;
-        mf(q);
-        constexpr int rd = nt4_read_at(q), dd = nt4_dma_at(q), md = nt4_dma_at(q + 1);
-        if constexpr (rd >= 0) {
-          constexpr int g = rd >> 3, r = rd & 7;
-          if constexpr (g == 0) fb1[r] = fragB(b, 1, r);
-          if constexpr (g == 1) fa1[r] = fragA(b, 1, r);
-          if constexpr (g == 2) fb0[r] = fragB(b ^ 1, 0, r);
-          if constexpr (g == 3) fa0[r] = fragA(b ^ 1, 0, r);
-        }
-        if constexpr (dd >= 0) dma_go(t + 2, dd);
-        if constexpr (md >= 0) m0_set(dma_lds(b, md));  // one MFMA ahead of its load
-        if constexpr (q == 19 || q == 50) {
-          __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-          if constexpr (q == 19) PRA_NT_STAMP(ts1);
-          __builtin_amdgcn_s_barrier();
-          if constexpr (q == 19) PRA_NT_STAMP(ts2);
-        }
-        if constexpr (q == 67) {
-          PRA_NT_STAMP(ts3);
-          wait_vm<18>();
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          PRA_NT_STAMP(ts4);
-        }
-        if constexpr (q == 104) {
-          wait_vm<15>();
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-#ifdef PRA_NT_STAMPS
-      sw1 += ts2 - ts1; sp2 += ts3 - ts2; sw2 += ts4 - ts3;
-      if (ts4p) sp31 += ts1 - ts4p;
-      ts4p = ts4; ++nch;
-#endif
     };
     // four chunks per iteration with compile-time buffers (a 2-chunk body with a conditional
     // second chunk broke the accumulator register coalescing: 100+ spills)
     for (int t = c0; t < c1; t += 4) {
-      if constexpr (PRA_NT_SCHED == 1) {
-        if (t < c1) chunk4(IC<0>{}, t);
-        if (t + 1 < c1) chunk4(IC<1>{}, t + 1);
-        if (t + 2 < c1) chunk4(IC<0>{}, t + 2);
-        if (t + 3 < c1) chunk4(IC<1>{}, t + 3);
-      } else {
-        if (t < c1) chunk(IC<0>{}, t);
-        if (t + 1 < c1) chunk(IC<1>{}, t + 1);
-        if (t + 2 < c1) chunk(IC<0>{}, t + 2);
-        if (t + 3 < c1) chunk(IC<1>{}, t + 3);
-      }
+      if (t < c1) chunk(IC<0>{}, t);
+      if (t + 1 < c1) chunk(IC<1>{}, t + 1);
+      if (t + 2 < c1) chunk(IC<0>{}, t + 2);
+      if (t + 3 < c1) chunk(IC<1>{}, t + 3);
     }
     // no LDS-DMA may land after this point, and no wave may still read a buffer the split
     // tail's flag overwrites
@@ -846,80 +639,47 @@ __global__ __launch_bounds__(NTH) void gemm_nt_kernel(const T* __restrict__ A, c
 #endif
 }
 
-__global__ __launch_bounds__(256) void zero_i32_kernel(int* __restrict__ p, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 }  // namespace nt
 }  // namespace pra
 
 extern "C" {
 
-// fp32 partial-tile floats and tickets the split tail of an [M, N, K] NT GEMM needs (0 = none)
-long pra_gemm_nt_ws_floats(int M, int N, int K, int cus) {
-  using namespace pra::gm;
-  const int nwg = (M / BM) * (N / BN);
-  const int S = pra::gemm_tail_split(nwg, cus, K / BK, 2);
-  return S > 1 ? (long)(nwg % cus) * S * BM * BN : 0;
-}
-int pra_gemm_nt_ticket_count(int M, int N, int K, int cus) {
-  using namespace pra::gm;
-  const int nwg = (M / BM) * (N / BN);
-  return pra::gemm_tail_split(nwg, cus, K / BK, 2) > 1 ? nwg % cus : 0;
+void pra_gemm_scratch(int kind, int M, int N, int K, int cus, long* ws_floats, int* tickets) {
+  const pra::GemmPlan p = pra::gemm_plan(kind, M, N, K, cus);
+  *ws_floats = p.ws_floats;
+  *tickets = p.tickets;
 }
 
-// C = A B^T with the epilogue `epi` (see the file comment). A [M][K] (row stride lda), B [N][K]
-// (ldb), C [M][N] (ldc; EPI 1: gu [M][2F] with N = 2F, EPI 2: gu [M][2F] with N = F).
-// ws/tickets: sized by pra_gemm_nt_ws_floats / pra_gemm_nt_ticket_count (null when those are 0).
-hipError_t pra_gemm_nt(int dtype, int epi, const void* A, const void* B, void* C, int M, int N, int K, long lda,
-                       long ldb, long ldc, void* c2, long ldc2, int F, const void* tab, int S, int D, int nrot,
-                       float* ws, int* tickets, int cus, hipStream_t s) {
+hipError_t pra_gemm_nt(const pra_gemm_args* args, hipStream_t s) {
   using namespace pra::gm;
-  if (M % BM || N % BN || K % BK || K <= 0 || lda % 8 || ldb % 8 || ldc % 8 || cus <= 0) return hipErrorInvalidValue;
-  if (epi < 0 || epi > 3) return hipErrorInvalidValue;
-  if (epi == 1 && (N != 2 * F || F % 128 || c2 == nullptr || ldc2 % 8)) return hipErrorInvalidValue;
-  if (epi == 2 && (F != N || ldc < 2L * F)) return hipErrorInvalidValue;
-  if (epi == 3 && (tab == nullptr || S <= 0 || D % 8 || D <= 0 || nrot % D || nrot > N)) return hipErrorInvalidValue;
-  // per-lane DMA offsets are 32-bit byte offsets from the tile's row base
-  const long brows = epi == 1 ? (long)F + 128 : 256;
-  if (255L * lda * 2 + 2L * K > 0xffffffffL || brows * ldb * 2 + 2L * K > 0xffffffffL) return hipErrorInvalidValue;
-  const int nwg = (M / BM) * (N / BN);
-  // 128-B-row chunks whenever K allows; the 64-B-row stage ring serves K % 64 == 32
-  const int KBx = K % 64 == 0 ? 64 : 32;
-  const int Ssplit = pra::gemm_tail_split(nwg, cus, K / KBx, 2);
-  const int n_split = Ssplit > 1 && ws && tickets ? nwg % cus : 0;
-  const int Sx = n_split ? Ssplit : 1;
-  if (n_split)
-    hipLaunchKernelGGL(pra::nt::zero_i32_kernel, dim3((n_split + 255) / 256), dim3(256), 0, s, tickets, n_split);
-  const dim3 grid(nwg - n_split + n_split * Sx), block(NTH);
-#define PRA_NT_LAUNCH(TT, E)                                                                                  \
-  {                                                                                                           \
-    pra::nt::Epi<TT> ep{(TT*)c2, ldc2, F, (const float2*)tab, S, D, nrot};                                    \
-    if (KBx == 64)                                                                                            \
-      hipLaunchKernelGGL((pra::nt::gemm_nt_kernel<TT, E, 64>), grid, block, 0, s, (const TT*)A, (const TT*)B,  \
-                         (TT*)C, M, N, K, lda, ldb, ldc, ep, ws, tickets, n_split, Sx);                       \
-    else                                                                                                      \
-      hipLaunchKernelGGL((pra::nt::gemm_nt_kernel<TT, E, 32>), grid, block, 0, s, (const TT*)A, (const TT*)B,  \
-                         (TT*)C, M, N, K, lda, ldb, ldc, ep, ws, tickets, n_split, Sx);                       \
-  }
-#define PRA_NT_EPI(TT)                   \
-  switch (epi) {                         \
-    case 0: PRA_NT_LAUNCH(TT, 0) break;  \
-    case 1: PRA_NT_LAUNCH(TT, 1) break;  \
-    case 2: PRA_NT_LAUNCH(TT, 2) break;  \
-    default: PRA_NT_LAUNCH(TT, 3) break; \
-  }
-  if (dtype == pra::kBF16) {
-    PRA_NT_EPI(__bf16)
-  } else if (dtype == pra::kF16) {
-    PRA_NT_EPI(_Float16)
-  } else {
+  const pra_gemm_args a = *args;
+  if (!gemm_args_ok(a) || a.accumulate) return hipErrorInvalidValue;
+  if (a.epi < 0 || a.epi > 3) return hipErrorInvalidValue;
+  if (a.epi == 1 && (a.N != 2 * a.F || a.F % 128 || a.c2 == nullptr || a.ldc2 % 8)) return hipErrorInvalidValue;
+  if (a.epi == 2 && (a.F != a.N || a.ldc < 2L * a.F)) return hipErrorInvalidValue;
+  if (a.epi == 3 && (a.tab == nullptr || a.S <= 0 || a.D % 8 || a.D <= 0 || a.nrot % a.D || a.nrot > a.N))
     return hipErrorInvalidValue;
-  }
-#undef PRA_NT_EPI
-#undef PRA_NT_LAUNCH
-  return hipGetLastError();
+  // per-lane DMA offsets are 32-bit byte offsets from the tile's row base
+  const long brows = a.epi == 1 ? (long)a.F + 128 : 256;
+  if (255L * a.lda * 2 + 2L * a.K > 0xffffffffL || brows * a.ldb * 2 + 2L * a.K > 0xffffffffL)
+    return hipErrorInvalidValue;
+  // 128-B-row chunks whenever K allows; the 64-B-row stage ring serves K % 64 == 32 (GemmPlan::kb)
+  const pra::GemmPlan pl = gemm_launch_plan(pra::kGemmNT, a);
+  if (pl.n_split) zero_tickets(a.tickets, pl.n_split, s);
+  const hipError_t e = dispatch_elem(a.dtype, [&](auto t) {
+    using T = decltype(t);
+    const pra::nt::Epi<T> ep{(T*)a.c2, a.ldc2, a.F, (const float2*)a.tab, a.S, a.D, a.nrot};
+    pra::dispatch(
+        [&](auto epi, auto kb) {
+          hipLaunchKernelGGL((pra::nt::gemm_nt_kernel<T, epi(), kb()>), dim3(pl.grid), dim3(NTH), 0, s, (const T*)a.a,
+                             (const T*)a.b, (T*)a.c, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, ep, a.ws, a.tickets, pl.n_split,
+                             pl.S);
+        },
+        // (instantiations come out last value first: EPI 0..3, each 64 then 32, as they always have)
+        pra::One<3, 2, 1, 0>{a.epi}, pra::One<32, 64>{pl.kb});
+    return hipSuccess;
+  });
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // extern "C"

@@ -66,19 +66,13 @@ __device__ __forceinline__ i16x4 tr4(const T* tile, int byte_off) {
 // ws and takes a ticket; the last arriver of a tile sums the S partials in part order (its own from
 // ws too) -- deterministic, and nothing ever waits on another
 // workgroup.
-// EXP (timing experiments only, tools/gemm_exp.py; results are garbage): bit 0 = no main-loop
-// LDS-DMA (prologue stages only), bit 1 = no main-loop fragment reads (stale registers)
-// 1: each DMA group's M0 write first, its load last (no s_nop): 4096x4096x32768 1481-1509 -> 1514-1538
-// TF, 11008x4096x32768 1366-1376 -> 1407-1410 TF (tools/wgrad_variants.hip,
-// profiles/r4/wgrad_m0split_ab.log)
-#ifndef PRA_WG_SMAX
-#define PRA_WG_SMAX 2  // largest K-split of a partial last round (W2 at 4: 11% slower, profiles/r4/wgrad_w2_tail_split_ab.log)
-#endif
-#ifndef PRA_WG_M0SPLIT
-#define PRA_WG_M0SPLIT 1
-#endif
+// Timing experiments at 32768 x 4096 x 16384 (instantiations with parts of the main loop left out,
+// results garbage; removed): 1.40 PF as is, 1.78 PF without the main-loop LDS-DMA, 1.53 PF without the
+// fragment reads (profiles/r3/gemm_wgrad_exp.log).
+// Each DMA's M0 write next to its load (s_nop as the wait state): 4096x4096x32768 1481-1509 vs 1514-1538
+// TF, 11008x4096x32768 1366-1376 vs 1407-1410 TF: measured slower: profiles/r4/wgrad_m0split_ab.log
 
-template <typename T, bool ACC, int EXP = 0>
+template <typename T, bool ACC>
 __global__ __launch_bounds__(NTH) void wgrad16_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                       T* __restrict__ C, int M, int N, int K, long lda, long ldb,
                                                       long ldc, float* __restrict__ ws, int* __restrict__ tickets,
@@ -177,22 +171,18 @@ __global__ __launch_bounds__(NTH) void wgrad16_kernel(const T* __restrict__ A, c
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = mfma16(cb[j], ca[i], acc[i][j]);
-      if constexpr (!(EXP & 1)) wait_vm<2 * NI * (NS - 3)>();  // stage kt + 1 landed
+      wait_vm<2 * NI * (NS - 3)>();  // stage kt + 1 landed
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       const int kd = min(kt + NS - 1, k1 - 1);
 #pragma unroll
       for (int gi = 0; gi < 8; ++gi) {
-        // PRA_WG_M0SPLIT: the group's M0 write goes first and its DMA last, so the group's MFMAs
-        // are the wait state (no s_nop)
-        if constexpr (PRA_WG_M0SPLIT && !(EXP & 1)) {
-          m0_set(dma_lds(sd, gi));
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (!(EXP & 2)) {
-          na[gi] = fragA(nta, gi);
-          nb[gi] = fragB(nta + TILE, gi);
-        }
+        // the group's M0 write goes first and its DMA last, so the group's MFMAs are the wait
+        // state (no s_nop)
+        m0_set(dma_lds(sd, gi));
+        __builtin_amdgcn_sched_barrier(0);
+        na[gi] = fragA(nta, gi);
+        nb[gi] = fragB(nta + TILE, gi);
         const int i = 4 + (gi >> 1);
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) {
@@ -204,12 +194,8 @@ __global__ __launch_bounds__(NTH) void wgrad16_kernel(const T* __restrict__ A, c
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
-        if constexpr (PRA_WG_M0SPLIT && !(EXP & 1))
-          dma_go(kd, gi);
-        else if constexpr (!(EXP & 1))
-          dma(sd, kd, gi);
+        dma_go(kd, gi);
       }
-
     };
     // unrolled by lcm(NS, 2) = 10: compile-time ring slot and fragment register set
     constexpr int UNR = 10;
@@ -330,12 +316,6 @@ __global__ __launch_bounds__(NTH) void wgrad16_kernel(const T* __restrict__ A, c
   store_c(m0, n0);
 }
 
-// zeroes the split tail's tickets (a kernel node, ordered before the GEMM in a captured graph)
-__global__ __launch_bounds__(256) void zero_i32_kernel(int* __restrict__ p, int n) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) p[i] = 0;
-}
-
 }  // namespace wg
 }  // namespace pra
 
@@ -344,75 +324,28 @@ __global__ __launch_bounds__(256) void zero_i32_kernel(int* __restrict__ p, int 
 // profiles/r5/wgrad_bench_7b*.log, wgrad_bench_8b_b1.log. Removed in round 6.)
 extern "C" {
 
-// C[M][N] (+)= A^T B with A [K][M] (row stride lda), B [K][N] (row stride ldb), C row stride ldc.
-// ws / tickets: sized by pra_wgrad_ws_floats / pra_wgrad_ticket_count (the split tail; both may be
-// null, then the tail runs as a partial data-parallel round).
-// fp32 partial-tile floats / tickets the split tail of an [M, N, K] weight gradient needs (0 = none)
-long pra_wgrad_ws_floats(int M, int N, int K, int cus) {
+hipError_t pra_wgrad_gemm(const pra_gemm_args* args, hipStream_t s) {
   using namespace pra::gm;
-  const int nwg = (M / BM) * (N / BN);
-  const int S = pra::gemm_tail_split(nwg, cus, K / BK, PRA_WG_SMAX);
-  return S > 1 ? (long)(nwg % cus) * S * BM * BN : 0;
-}
-int pra_wgrad_ticket_count(int M, int N, int K, int cus) {
-  using namespace pra::gm;
-  const int nwg = (M / BM) * (N / BN);
-  return pra::gemm_tail_split(nwg, cus, K / BK, PRA_WG_SMAX) > 1 ? nwg % cus : 0;
-}
-
-hipError_t pra_wgrad_gemm(int dtype, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
-                          long ldc, int accumulate, float* ws, int* tickets, int cus, hipStream_t s) {
-  using namespace pra::gm;
-  if (M % BM || N % BN || K % BK || K <= 0 || lda % 8 || ldb % 8 || ldc % 8 || cus <= 0) return hipErrorInvalidValue;
-  if ((long)(BK - 1) * lda + M > 0x7fffffffL || (long)(BK - 1) * ldb + N > 0x7fffffffL) return hipErrorInvalidValue;
-  const int nwg = (M / BM) * (N / BN);
-  // split the tiles of a partial last round S ways over K (S <= 2; 7B shapes: W13's 96 tail tiles
-  // S = 2, 1.31 -> 1.40 PF; W2's 176 would need S = 4, measured slower, so unsplit)
-  const int Sx = pra::gemm_tail_split(nwg, cus, K / BK, PRA_WG_SMAX);
-  const int n_split = Sx > 1 && ws && tickets ? nwg % cus : 0;
-  const int S = n_split ? Sx : 1;
-  // tickets are zeroed by a kernel, not hipMemsetAsync: replayed from a captured HIP graph
-  // (train.py --compile), the memset node's zeros were not seen by the GEMM's ticket atomics and
-  // most split tiles were never reduced (tests/test_kernels_gpu.py, graph-capture test)
-  if (n_split) hipLaunchKernelGGL(pra::wg::zero_i32_kernel, dim3((n_split + 255) / 256), dim3(256), 0, s, tickets, n_split);
-  const dim3 grid(nwg - n_split + n_split * S), block(NTH);
-#define PRA_WG_LAUNCH(TT)                                                                                    \
-  if (accumulate)                                                                                            \
-    hipLaunchKernelGGL((pra::wg::wgrad16_kernel<TT, true>), grid, block, 0, s, (const TT*)A, (const TT*)B,     \
-                       (TT*)C, M, N, K, lda, ldb, ldc, ws, tickets, n_split, S);                             \
-  else                                                                                                       \
-    hipLaunchKernelGGL((pra::wg::wgrad16_kernel<TT, false>), grid, block, 0, s, (const TT*)A, (const TT*)B,    \
-                       (TT*)C, M, N, K, lda, ldb, ldc, ws, tickets, n_split, S);
-  if (dtype == pra::kBF16) {
-    PRA_WG_LAUNCH(__bf16)
-  } else if (dtype == pra::kF16) {
-    PRA_WG_LAUNCH(_Float16)
-  } else {
+  const pra_gemm_args a = *args;
+  if (!gemm_args_ok(a) || a.epi) return hipErrorInvalidValue;
+  if ((long)(BK - 1) * a.lda + a.M > 0x7fffffffL || (long)(BK - 1) * a.ldb + a.N > 0x7fffffffL)
     return hipErrorInvalidValue;
-  }
-#undef PRA_WG_LAUNCH
-  return hipGetLastError();
-}
-
-// timing experiments (see wgrad16_kernel's EXP): bf16, no accumulate, no split tail. Measured at
-// 32768 x 4096 x 16384: 1.40 PF as is, 1.78 PF without the main-loop LDS-DMA, 1.53 PF without the
-// fragment reads (profiles/r3/gemm_wgrad_exp.log)
-hipError_t pra_wgrad_gemm_exp(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
-                              long ldc, int exp, hipStream_t s) {
-  using namespace pra::gm;
-  if (M % BM || N % BN || K % BK || K <= 0 || lda % 8 || ldb % 8 || ldc % 8) return hipErrorInvalidValue;
-  const dim3 grid((M / BM) * (N / BN)), block(NTH);
-#define PRA_WG_EXP(E)                                                                                        \
-  hipLaunchKernelGGL((pra::wg::wgrad16_kernel<__bf16, false, E>), grid, block, 0, s, (const __bf16*)A,         \
-                     (const __bf16*)B, (__bf16*)C, M, N, K, lda, ldb, ldc, nullptr, nullptr, 0, 1)
-  switch (exp) {
-    case 1: PRA_WG_EXP(1); break;
-    case 2: PRA_WG_EXP(2); break;
-    case 3: PRA_WG_EXP(3); break;
-    default: PRA_WG_EXP(0); break;
-  }
-#undef PRA_WG_EXP
-  return hipGetLastError();
+  // the tiles of a partial last round split S ways over K (S <= 2; 7B shapes: W13's 96 tail tiles
+  // S = 2, 1.31 -> 1.40 PF; W2's 176 would need S = 4, measured slower, so unsplit)
+  const pra::GemmPlan pl = gemm_launch_plan(pra::kGemmWgrad, a);
+  if (pl.n_split) zero_tickets(a.tickets, pl.n_split, s);
+  const hipError_t e = dispatch_elem(a.dtype, [&](auto t) {
+    using T = decltype(t);
+    pra::dispatch(
+        [&](auto acc) {
+          hipLaunchKernelGGL((pra::wg::wgrad16_kernel<T, acc() != 0>), dim3(pl.grid), dim3(NTH), 0, s, (const T*)a.a,
+                             (const T*)a.b, (T*)a.c, a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.ws, a.tickets, pl.n_split,
+                             pl.S);
+        },
+        pra::One<0, 1>{a.accumulate != 0});
+    return hipSuccess;
+  });
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "attn_plan.h"
+#include "gemm_plan.h"
 
 extern "C" {
 int pra_rmsnorm_bwd_ws_extra();
@@ -40,22 +41,38 @@ hipError_t pra_swiglu_bwd_t(int dtype, const void* dy, void* gu, void* guT, long
 hipError_t pra_rope_t(int dtype, void* x, void* xT, const void* tab, long ntok, int ld, int ncols, int nrot, int D,
                       int S, int inverse, hipStream_t s);
 hipError_t pra_transpose16(const void* src, void* dst, long R, long C, long ld_src, long ld_dst, hipStream_t s);
-// C[M][N] (+)= A^T B, A [K][M], B [K][N] row-major (weight gradient on row-major activations);
-// M, N multiples of 256, K of 32 (gemm_wgrad.hip)
-hipError_t pra_wgrad_gemm(int dtype, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
-                          long ldc, int accumulate, float* ws, int* tickets, int cus, hipStream_t s);
-hipError_t pra_wgrad_gemm_exp(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb,
-                              long ldc, int exp, hipStream_t s);
-long pra_wgrad_ws_floats(int M, int N, int K, int cus);
-int pra_wgrad_ticket_count(int M, int N, int K, int cus);
-// C = A B^T, A [M][K], B [N][K] (both K-contiguous) with a fused epilogue (gemm_nt.hip):
-// epi 0 plain, 1 SwiGLU forward (C = gu [M][2F], c2 = a [M][F]), 2 SwiGLU backward in place over
-// gu (C), 3 RoPE on the first nrot columns (tab float2 [S][D/2])
-hipError_t pra_gemm_nt(int dtype, int epi, const void* A, const void* B, void* C, int M, int N, int K, long lda,
-                       long ldb, long ldc, void* c2, long ldc2, int F, const void* tab, int S, int D, int nrot,
-                       float* ws, int* tickets, int cus, hipStream_t s);
-long pra_gemm_nt_ws_floats(int M, int N, int K, int cus);
-int pra_gemm_nt_ticket_count(int M, int N, int K, int cus);
+// The hand-written GEMMs, bf16 / fp16, M and N multiples of 256, K of 32, leading dimensions in elements
+// (% 8). The launchers read the block before they return and keep no pointer to it (graph capture).
+//   pra_gemm_nt (gemm_nt.hip):       C[M][N] = A B^T with A [M][K], B [N][K], both K-contiguous, and a
+//                                    fused epilogue; accumulate must be 0
+//   pra_wgrad_gemm (gemm_wgrad.hip): C[M][N] (+)= A^T B with A [K][M], B [K][N] row-major (the weight
+//                                    gradient on row-major activations); epi must be 0
+typedef struct pra_gemm_args {
+  int dtype;  // pra::kBF16 / kF16
+  int M, N, K;
+  const void* a; long lda;
+  const void* b; long ldb;
+  void* c; long ldc;
+  int accumulate;  // weight gradient: add the existing C in fp32 and round once (addmm's beta = 1)
+  // NT epilogue: 0 plain; 1 SwiGLU forward (b = W1|W3 [2F][K], c = gu [M][2F] with N = 2F, c2 = a [M][F]);
+  // 2 SwiGLU backward in place over c = gu [M][2F] (N = F, ldc >= 2F; da itself is never stored);
+  // 3 RoPE on the first nrot columns of c
+  int epi;
+  void* c2; long ldc2;  // epi 1: a = round(silu(g)) * u
+  int F;                // epi 1 / 2: gu holds g at [0, F) and u at [F, 2F)
+  const void* tab;      // epi 3: (cos, sin) float2 [S][D / 2]
+  int S, D, nrot;       // epi 3: row m sits at position m % S; head dim D % 8 == 0; nrot % D == 0, <= N
+  // Split tail (gemm_plan.h): pra_gemm_scratch floats / int32s, uninitialised. Either null: the tail
+  // tiles run unsplit.
+  float* ws;
+  int* tickets;
+  int cus;  // compute units of the device
+} pra_gemm_args;
+hipError_t pra_gemm_nt(const pra_gemm_args* a, hipStream_t s);
+hipError_t pra_wgrad_gemm(const pra_gemm_args* a, hipStream_t s);
+// kind: pra::GemmKind. Fills the fp32 floats and the tickets the split tail of an [M, N, K] GEMM takes
+// (both 0: no split)
+void pra_gemm_scratch(int kind, int M, int N, int K, int cus, long* ws_floats, int* tickets);
 
 hipError_t pra_xent_fwd(int dtype, const void* logits, const int64_t* labels, float* lse, float* loss_row,
                         float* stats, long T, long V, long ld, long ignore_index, hipStream_t s);

@@ -39,7 +39,7 @@ FP32_CAP = 2.0 ** -16
 FP16_FLUSH = 2.0 ** -24
 LOG2E = 1.4426950408889634
 
-# 16-bit roundings on the path to each output (default build: PRA_FWD_PRESCALE = PRA_DQ_PRESCALE = 0),
+# 16-bit roundings on the path to each output (the kernels scale the fp32 scores; no operand is pre-multiplied),
 # final store included.
 #   o   P -> T before P V          attention.hip:189 (fwd_kernel), :403 / :422 (fwd_p_kernel), attention_docs.hip:158
 #       final store                attention.hip:215, :483, attention_docs.hip:182 (attn_common.h:74 pack_x2)

@@ -29,6 +29,7 @@ def _rel_err(out, ref):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(256, 256, 32), (512, 768, 256), (1024, 512, 1056), (512, 512, 4160),
                                    (4096, 4352, 128),  # 272 tiles: split-K tail (S = 2)
+                                   (4096, 4352, 64),   # a partial last round of one 64-deep chunk: unsplit
                                    (2048, 256 * 33, 96)])
 def test_gemm_nt_plain_matches_oracle(cuda, dtype, M, N, K):
     C = _C()

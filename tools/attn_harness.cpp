@@ -1,5 +1,5 @@
 // Standalone attention benchmark + checker (no torch): links one build of csrc/kernels/attention.hip
-// (tools/attn_variants.sh builds one executable per -D variant) and times pra_attn_fwd / pra_attn_bwd
+// (tools/attn_variants.sh builds one executable per set of compiler flags) and times pra_attn_fwd / pra_attn_bwd
 // on random bf16 data with hipEvents, then checks one (batch, kv-head) group against an fp64 CPU
 // reference (O, LSE, dQ, dK, dV). Used to iterate on kernel schedules without rebuilding the torch
 // extension; the same kernels are what pyrecover_amd._C runs.

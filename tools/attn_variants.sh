@@ -1,7 +1,8 @@
 #!/bin/bash
-# Build one standalone attention harness per kernel variant (tools/attn_harness.cpp linked with
-# csrc/kernels/attention.hip compiled under the variant's -D flags), on the CPU host:
-#   tools/attn_variants.sh NAME="-DFLAG=1 ..." [NAME2="..."]   ->  build_gpu/attn_var/attn_<NAME>
+# Build one standalone attention harness per set of extra compiler flags (tools/attn_harness.cpp linked
+# with csrc/kernels/attention.hip and attention_bwd_fused.hip compiled under those flags; an empty set
+# builds the production kernels), on the CPU host:
+#   tools/attn_variants.sh NAME="FLAGS ..." [NAME2="..."]   ->  build_gpu/attn_var/attn_<NAME>
 # Run them on the GPU with tools/attn_variants_run.sh.
 set -eu
 cd "$(dirname "$0")/.."
@@ -11,7 +12,7 @@ HIPCC=${ROCM_PATH:-/opt/rocm}/bin/hipcc
 FL="-O3 -std=c++17 --offload-arch=gfx950 -Icsrc -Icsrc/kernels"
 AFL=${AFL-"-fno-honor-nans -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form"}
 # pra_attn_fwd / pra_attn_bwd (attention.hip) route to every family, so all of them are linked;
-# the fp32 and document-masked kernels have no variants and are built once
+# the fp32 and document-masked kernels are built once
 [ -f $OUT/attention_f32.o ] || $HIPCC $FL -c csrc/kernels/attention_f32.hip -o $OUT/attention_f32.o
 [ -f $OUT/attention_docs.o ] || $HIPCC $FL $AFL -c csrc/kernels/attention_docs.hip -o $OUT/attention_docs.o
 [ -f $OUT/harness.o -a $OUT/harness.o -nt tools/attn_harness.cpp ] || $HIPCC $FL -c tools/attn_harness.cpp -o $OUT/harness.o

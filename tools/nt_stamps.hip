@@ -65,12 +65,11 @@ int main(int argc, char** argv) {
   if (epi == 2) hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, C, 2L * M * N, 3u);
   hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, A, (long)M * K, 1u);
   hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, B, (long)N * K, 2u);
-  const long wsf = pra_gemm_nt_ws_floats(M, N, K, cus);
-  const int nt = pra_gemm_nt_ticket_count(M, N, K, cus);
+  const pra::GemmPlan pl = pra::gemm_plan(pra::kGemmNT, M, N, K, cus);
   float* ws = nullptr;
   int* tk = nullptr;
-  if (wsf) CK(hipMalloc(&ws, wsf * 4));
-  if (nt) CK(hipMalloc(&tk, nt * 4));
+  if (pl.ws_floats) CK(hipMalloc(&ws, pl.ws_floats * 4));
+  if (pl.tickets) CK(hipMalloc(&tk, pl.tickets * 4));
   const int nwg = (M / 256) * (N / 256);
   const long nst = 2L * nwg * 4 * 8;
   unsigned long long* st = nullptr;
@@ -88,12 +87,19 @@ int main(int argc, char** argv) {
 #endif
   __bf16* C2 = nullptr;
   if (epi == 1) CK(hipMalloc(&C2, (size_t)M * (N / 2) * 2));
-  auto launch = [&]() {
-    if (epi == 2)  // C is gu [M][2N], dg / du written over g / u launch after launch: timing only (the math is
-                   // checked by tests/test_gemm_nt_gpu.py)
-      return pra_gemm_nt(pra::kBF16, 2, A, B, C, M, N, K, K, K, 2L * N, nullptr, 0, N, nullptr, 0, 0, 0, ws, tk, cus, 0);
-    return pra_gemm_nt(pra::kBF16, epi, A, B, C, M, N, K, K, K, N, C2, N / 2, N / 2, nullptr, 0, 0, 0, ws, tk, cus, 0);
-  };
+  pra_gemm_args ga = {};
+  ga.dtype = pra::kBF16;
+  ga.M = M, ga.N = N, ga.K = K;
+  ga.a = A, ga.lda = K;
+  ga.b = B, ga.ldb = K;
+  // epi 2: C is gu [M][2N], dg / du written over g / u launch after launch: timing only (the math is
+  // checked by tests/test_gemm_nt_gpu.py)
+  ga.c = C, ga.ldc = epi == 2 ? 2L * N : N;
+  ga.epi = epi;
+  ga.c2 = epi == 2 ? nullptr : C2, ga.ldc2 = epi == 2 ? 0 : N / 2;
+  ga.F = epi == 2 ? N : N / 2;
+  ga.ws = ws, ga.tickets = tk, ga.cus = cus;
+  auto launch = [&]() { return pra_gemm_nt(&ga, 0); };
   CK(launch());
   CK(hipDeviceSynchronize());
   const auto t0 = std::chrono::steady_clock::now();

@@ -1,8 +1,8 @@
-// Standalone timing of the MFMA weight-gradient GEMM (csrc/kernels/gemm_wgrad.hip), for A/B of
-// compile-time schedule variants (-DPRA_WG_M0SPLIT=0/1): ~2 s of back-to-back launches on random
-// data (the GEMMs run at the power-limited clock), then 20 timed launches and a sampled fp32 check.
+// Standalone timing of the MFMA weight-gradient GEMM (csrc/kernels/gemm_wgrad.hip) without torch, for
+// A/B of two checkouts or compiler flag sets: ~2 s of back-to-back launches on random data (the GEMMs
+// run at the power-limited clock), then 20 timed launches and a sampled fp32 check.
 //
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Icsrc/kernels [-DPRA_WG_M0SPLIT=1] tools/wgrad_variants.hip -o wg
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Icsrc/kernels tools/wgrad_variants.hip -o wg
 //   ./wg [M N K [warm_seconds]]      C[M][N] = A^T B, A [K][M], B [K][N]
 #include "../csrc/kernels/gemm_wgrad.hip"
 
@@ -48,13 +48,19 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&C, (size_t)M * N * 2));
   hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, A, (long)K * M, 1u);
   hipLaunchKernelGGL(fill_bf16, dim3(4096), dim3(256), 0, 0, B, (long)K * N, 2u);
-  const long wsf = pra_wgrad_ws_floats(M, N, K, cus);
-  const int nt = pra_wgrad_ticket_count(M, N, K, cus);
+  const pra::GemmPlan pl = pra::gemm_plan(pra::kGemmWgrad, M, N, K, cus);
   float* ws = nullptr;
   int* tk = nullptr;
-  if (wsf) CK(hipMalloc(&ws, wsf * 4));
-  if (nt) CK(hipMalloc(&tk, nt * 4));
-  auto launch = [&]() { return pra_wgrad_gemm(pra::kBF16, A, B, C, M, N, K, M, N, N, 0, ws, tk, cus, 0); };
+  if (pl.ws_floats) CK(hipMalloc(&ws, pl.ws_floats * 4));
+  if (pl.tickets) CK(hipMalloc(&tk, pl.tickets * 4));
+  pra_gemm_args ga = {};
+  ga.dtype = pra::kBF16;
+  ga.M = M, ga.N = N, ga.K = K;
+  ga.a = A, ga.lda = M;
+  ga.b = B, ga.ldb = N;
+  ga.c = C, ga.ldc = N;
+  ga.ws = ws, ga.tickets = tk, ga.cus = cus;
+  auto launch = [&]() { return pra_wgrad_gemm(&ga, 0); };
   CK(launch());
   CK(hipDeviceSynchronize());
   const auto t0 = std::chrono::steady_clock::now();
@@ -81,8 +87,7 @@ int main(int argc, char** argv) {
   std::vector<float> he(4096);
   CK(hipMemcpy(he.data(), err, 4096 * 4, hipMemcpyDeviceToHost));
   const float maxerr = *std::max_element(he.begin(), he.end());
-  printf("{\"m0split\": %d, \"M\": %d, \"N\": %d, \"K\": %d, \"warm_launches\": %d, \"ms\": %.4f, \"tflops\": %.1f, "
-         "\"max_rel_err_4096_samples\": %.5f}\n", PRA_WG_M0SPLIT, M, N, K, nwarm, ms, 2.0 * M * N * K / (ms * 1e-3) / 1e12,
-         maxerr);
+  printf("{\"M\": %d, \"N\": %d, \"K\": %d, \"warm_launches\": %d, \"ms\": %.4f, \"tflops\": %.1f, "
+         "\"max_rel_err_4096_samples\": %.5f}\n", M, N, K, nwarm, ms, 2.0 * M * N * K / (ms * 1e-3) / 1e12, maxerr);
   return maxerr < 0.02f ? 0 : 2;
 }
