@@ -1018,6 +1018,118 @@ std::vector<at::Tensor> attn_decode(const at::Tensor& q, const at::Tensor& k_cac
   return {o, lse};
 }
 
+// fp8 KV cache (csrc/kernels/attention_decode_fp8.hip): the checks of check_decode_common with uint8 caches
+// [B, cap, Hkv, D] of e4m3fn bytes and fp32 scales [B, cap, Hkv]. kv_len: absent for the prefill store.
+void check_decode_fp8_common(const at::Tensor& ref, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& ks,
+                             const at::Tensor& vs, const at::Tensor* kv_len, int64_t B, const char* op) {
+  TORCH_CHECK(ref.scalar_type() == at::kBFloat16 || ref.scalar_type() == at::kHalf, op,
+              ": the HIP kernels take bf16 or fp16 (got ", ref.scalar_type(),
+              "); other dtypes run the torch math of pyrecover_amd.ops.reference");
+  same_dev(ref, kc, "k_cache");
+  same_dev(ref, vc, "v_cache");
+  same_dev(ref, ks, "k_scale");
+  same_dev(ref, vs, "v_scale");
+  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(1) > 0 && kc.size(2) > 0, op,
+              ": k_cache must be [B, cap, Hkv, D] with B = ", B, ", got ", kc.sizes());
+  TORCH_CHECK(vc.sizes() == kc.sizes(), op, ": v_cache must have k_cache's shape");
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), op, ": the caches must be contiguous");
+  TORCH_CHECK(kc.scalar_type() == at::kByte && vc.scalar_type() == at::kByte, op,
+              ": the fp8 caches must have dtype uint8 (e4m3fn bytes)");
+  TORCH_CHECK(kc.size(3) == 64 || kc.size(3) == 128, op, ": head_dim must be 64 or 128");
+  TORCH_CHECK(kc.size(1) <= (int64_t)INT32_MAX / 2 && kc.size(2) <= 65535 && B > 0 && B <= 65535, op, ": bad shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0,
+              op, ": the caches must be 16-B aligned");
+  for (const at::Tensor* s : {&ks, &vs})
+    TORCH_CHECK(s->scalar_type() == at::kFloat && s->dim() == 3 && s->size(0) == B && s->size(1) == kc.size(1) &&
+                    s->size(2) == kc.size(2) && s->is_contiguous(),
+                op, ": k_scale and v_scale must be contiguous fp32 [B, cap, Hkv], got ", s->sizes());
+  if (kv_len != nullptr) {
+    same_dev(ref, *kv_len, "kv_len");
+    TORCH_CHECK(kv_len->scalar_type() == at::kInt && kv_len->dim() == 1 && kv_len->size(0) == B &&
+                    kv_len->is_contiguous(),
+                op, ": kv_len must be contiguous int32 [B]");
+  }
+}
+
+// k, v [B, S, Hkv, D]: the k and v views of the fused QKV activation [B * S, ld] (or any tensors with that
+// stride pattern) quantized into rows 0 .. S - 1 of the fp8 caches.
+void kv_quantize_(const at::Tensor& k, const at::Tensor& v, at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale,
+                  at::Tensor v_scale) {
+  const Range range_("pyrecover::kv_quantize");
+  check_dev(k, "k");
+  TORCH_CHECK(k.dim() == 4, "kv_quantize: k must be [B, S, Hkv, D], got ", k.sizes());
+  const int64_t B = k.size(0), S = k.size(1), Hkv = k.size(2), D = k.size(3);
+  check_decode_fp8_common(k, k_cache, v_cache, k_scale, v_scale, nullptr, B, "kv_quantize");
+  same_dev(k, v, "v");
+  TORCH_CHECK(v.sizes() == k.sizes() && v.scalar_type() == k.scalar_type() && v.strides() == k.strides(),
+              "kv_quantize: v must have k's shape, dtype and strides");
+  TORCH_CHECK(k_cache.size(2) == Hkv && k_cache.size(3) == D, "kv_quantize: k and the caches disagree on [Hkv, D]");
+  TORCH_CHECK(S > 0 && S <= k_cache.size(1), "kv_quantize: ", S, " rows do not fit the cache capacity ", k_cache.size(1));
+  const int64_t ld = k.stride(1);
+  TORCH_CHECK(k.stride(3) == 1 && k.stride(2) == D && ld >= Hkv * D && ld % 8 == 0 && (B == 1 || k.stride(0) == S * ld),
+              "kv_quantize: k and v must be [B, S, Hkv, D] views of rows [B * S, ld] with ld a multiple of 8 elements");
+  TORCH_CHECK(B * S <= (int64_t)INT32_MAX / 2, "kv_quantize: bad shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(k.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0,
+              "kv_quantize: k and v must be 16-B aligned");
+  const c10::DeviceGuard guard(k.device());
+  check(pra_kv_quantize(dt(k), k.data_ptr(), v.data_ptr(), ld, k_cache.data_ptr(), v_cache.data_ptr(),
+                        k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)B, (int)S, (int)Hkv, (int)D,
+                        (int)k_cache.size(1), stream_of(k)),
+        "kv_quantize");
+}
+
+// rope_append_ over an fp8 cache: q rotated in place (bit-equal), the rotated k row rounded to qkv's dtype and
+// the plain v row quantized into cache row clamp(kv_len[b], 0, cap - 1).
+void rope_append_fp8_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_len, at::Tensor k_cache,
+                      at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale) {
+  const Range range_("pyrecover::rope_append_fp8");
+  check_dev(qkv, "qkv");
+  check_row_major(qkv, "rope_append_fp8 qkv");
+  const int64_t B = qkv.size(0);
+  check_decode_fp8_common(qkv, k_cache, v_cache, k_scale, v_scale, &kv_len, B, "rope_append_fp8");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(qkv.size(1) % D == 0 && qkv.size(1) / D > 2 * Hkv && (qkv.size(1) / D - 2 * Hkv) % Hkv == 0,
+              "rope_append_fp8: qkv must be [B, (Hq + 2 Hkv) D] with Hq a multiple of Hkv, got ", qkv.sizes());
+  TORCH_CHECK(qkv.stride(0) % 8 == 0, "rope_append_fp8: the qkv row stride must be a multiple of 8 elements");
+  const int64_t Hq = qkv.size(1) / D - 2 * Hkv;
+  same_dev(qkv, tab, "rope table");
+  TORCH_CHECK(tab.scalar_type() == at::kFloat && tab.is_contiguous() && tab.dim() == 3 && tab.size(0) >= cap &&
+                  tab.size(1) == D / 2 && tab.size(2) == 2,
+              "rope_append_fp8: table must be contiguous fp32 [>= cap, D/2, 2]");
+  const c10::DeviceGuard guard(qkv.device());
+  check(pra_rope_append_fp8(dt(qkv), qkv.data_ptr(), tab.data_ptr(), kv_len.data_ptr<int>(), k_cache.data_ptr(),
+                            v_cache.data_ptr(), k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)B,
+                            qkv.stride(0), (int)Hq, (int)Hkv, (int)D, (int)cap, stream_of(qkv)),
+        "rope_append_fp8");
+}
+
+// attn_decode over an fp8 cache -> (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq]).
+std::vector<at::Tensor> attn_decode_fp8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& kv_len,
+                                        double scale) {
+  const Range range_("pyrecover::attn_decode_fp8");
+  check_dev(q, "q");
+  TORCH_CHECK(q.dim() == 3, "attn_decode_fp8: q must be [B, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  check_decode_fp8_common(q, k_cache, v_cache, k_scale, v_scale, &kv_len, B, "attn_decode_fp8");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "attn_decode_fp8: q and the caches disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_decode_fp8: n_heads must be a multiple of n_kv_heads");
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_decode_fp8: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, Hq}, q.options().dtype(at::kFloat));
+  at::Tensor ws = at::empty({pra_attn_decode_ws_floats((int)B, (int)Hq, (int)D, (int)cap)},
+                            q.options().dtype(at::kFloat));
+  check(pra_attn_decode_fp8(dt(q), qc.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr<float>(),
+                            v_scale.data_ptr<float>(), kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(),
+                            ws.data_ptr<float>(), (int)B, (int)Hq, (int)Hkv, (int)D, (int)cap, (float)scale,
+                            stream_of(q)),
+        "attn_decode_fp8");
+  return {o, lse};
+}
+
 // Device-side sampling (csrc/kernels/sample.hip): logits [B, V] bf16 / fp16 (row stride >= V) -> tok int64 [B].
 // temperature 0 is greedy; otherwise pos (int32 [B]) or, with the generation state, prompt_len + count
 // indexes the Philox draw. ws: int32 workspace of sample_ws_bytes(B) bytes (allocated here when absent).
@@ -1232,6 +1344,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"));
   m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
+  m.def("kv_quantize_", &kv_quantize_, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("k_scale"), py::arg("v_scale"));
+  m.def("rope_append_fp8_", &rope_append_fp8_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"));
+  m.def("attn_decode_fp8", &attn_decode_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"));
+  m.def("attn_decode_fp8_chunk", []() { return pra_attn_decode_fp8_chunk(); });
   m.def("sample_", &sample_, py::arg("logits"), py::arg("tok"), py::arg("temperature"), py::arg("top_k"),
         py::arg("top_p"), py::arg("seed"), py::arg("pos") = py::none(), py::arg("ws") = py::none(),
         py::arg("u_out") = py::none(), py::arg("done") = py::none(), py::arg("count") = py::none(),

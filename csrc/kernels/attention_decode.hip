@@ -380,4 +380,22 @@ hipError_t pra_attn_decode(int dtype, const void* q, const void* k_cache, const 
   });
   return hipErrorInvalidValue;
 }
+
+// The combine kernel alone, over partials that another chunk kernel wrote in this file's workspace layout
+// with this file's chunk length (attention_decode_fp8.hip).
+hipError_t pra_attn_decode_combine(int dtype, const float* ws_o, const float* ws_ml, const int* kv_len, void* o,
+                                   float* lse, int B, int Hq, int D, int cap, int NC, hipStream_t s) {
+  if (B <= 0 || Hq <= 0 || B > 65535 || NC != (cap + pra::kKC - 1) / pra::kKC) return hipErrorInvalidValue;
+  PRA_DISPATCH_16BIT(dtype, T, {
+    if (D == 64)
+      hipLaunchKernelGGL((pra::attn_decode_combine_kernel<T, 64>), dim3(Hq, B), dim3(64), 0, s, ws_o, ws_ml, kv_len,
+                         (T*)o, lse, Hq, cap, NC);
+    else if (D == 128)
+      hipLaunchKernelGGL((pra::attn_decode_combine_kernel<T, 128>), dim3(Hq, B), dim3(128), 0, s, ws_o, ws_ml, kv_len,
+                         (T*)o, lse, Hq, cap, NC);
+    else
+      return hipErrorInvalidValue;
+  });
+  return hipGetLastError();
+}
 }

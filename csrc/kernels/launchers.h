@@ -187,6 +187,24 @@ hipError_t pra_attn_decode(int dtype, const void* q, const void* k_cache, const 
                            hipStream_t s);
 long pra_attn_decode_ws_floats(int B, int Hq, int D, int cap);
 int pra_attn_decode_chunk();
+// the merge of pra_attn_decode alone: ws_o [B][Hq][NC][D], ws_ml [B][Hq][NC][2], NC = ceil(cap / chunk)
+hipError_t pra_attn_decode_combine(int dtype, const float* ws_o, const float* ws_ml, const int* kv_len, void* o,
+                                   float* lse, int B, int Hq, int D, int cap, int NC, hipStream_t s);
+
+// fp8 KV cache (attention_decode_fp8.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D] of
+// e4m3fn bytes, k_scale, v_scale fp32 [B][cap][Hkv], powers of two. dtype is the 16-bit type of qkv / q / o.
+// D 64 or 128. kv_quantize: k, v [B * S][ld] views of the fused QKV activation (Hkv * D columns each,
+// ld % 8 == 0) into cache rows 0 .. S - 1 (S <= cap). rope_append_fp8 and attn_decode_fp8 are
+// pra_rope_append / pra_attn_decode over this cache, same workspace.
+hipError_t pra_kv_quantize(int dtype, const void* k, const void* v, long ld, void* k_cache, void* v_cache,
+                           float* k_scale, float* v_scale, int B, int S, int Hkv, int D, int cap, hipStream_t s);
+hipError_t pra_rope_append_fp8(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
+                               float* k_scale, float* v_scale, int B, long ld, int Hq, int Hkv, int D, int cap,
+                               hipStream_t s);
+hipError_t pra_attn_decode_fp8(int dtype, const void* q, const void* k_cache, const void* v_cache,
+                               const float* k_scale, const float* v_scale, const int* kv_len, void* o, float* lse,
+                               float* ws, int B, int Hq, int Hkv, int D, int cap, float scale, hipStream_t s);
+int pra_attn_decode_fp8_chunk();
 
 // Device-side sampling (sample.hip documents the rule), bf16 / fp16 logits [B][ld], ld >= V >= 1, no
 // alignment demand beyond the element. The launcher copies the block before it returns (graph capture).

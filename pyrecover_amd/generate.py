@@ -2,7 +2,7 @@
 
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
         --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
-        [--sampler philox --decode-graph]
+        [--sampler philox --decode-graph] [--kv-cache-dtype fp8]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
 ``--model-dtype``, ``--tokenizer-name-or-path``) and the checkpoint flags (``--checkpoint-dir``,
@@ -25,7 +25,7 @@ from .ckpt.model_only import load_model_only
 from .cli import PRECISION_STR_TO_DTYPE, build_parser as train_parser, set_default_dtype
 from .config import get_preset
 from .data.tokenizer import load_tokenizer
-from .inference import generate
+from .inference import KV_DTYPES, generate
 from .models.llama import Transformer
 
 logger = logging.getLogger("pyrecover")
@@ -71,6 +71,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--decode-graph", action="store_true",
                    help="replay sample + decode step as one hipGraph per token (needs --sampler philox or "
                         "--temperature 0, and a bf16 / fp16 GPU model)")
+    p.add_argument("--kv-cache-dtype", choices=KV_DTYPES, default="model",
+                   help="model: the cache holds k / v in the model's dtype. fp8: e4m3fn bytes with one "
+                        "power-of-two scale per (token, kv head), about half the cache memory; the prompt's "
+                        "attention stays unquantized, so the first generated token does not change")
     p.add_argument("--no-kv-cache", action="store_true",
                    help="naive path: a full forward over the whole prefix per new token (debugging aid)")
     p.add_argument("--output-jsonl", type=str, default=None,
@@ -104,13 +108,15 @@ def main(argv=None) -> int:
     stats = {}
     tokens, reasons = generate(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                top_p=args.top_p, seed=args.seed, eos_id=eos, use_cache=not args.no_kv_cache,
-                               stats=stats, sampler=args.sampler, graph=args.decode_graph)
+                               stats=stats, sampler=args.sampler, graph=args.decode_graph,
+                               kv_cache_dtype=args.kv_cache_dtype)
     records = []
     for p, ids, why in zip(prompts, tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None
         records.append({"prompt_ids": list(p), "generated_ids": ids, "text": text, "finish_reason": why,
                         "prefill_ms": stats["prefill_ms"], "decode_ms_per_token": stats["decode_ms_per_token"],
-                        "checkpoint_step": step, "sampler": args.sampler, "decode_graph": args.decode_graph})
+                        "checkpoint_step": step, "sampler": args.sampler, "decode_graph": args.decode_graph,
+                        "kv_cache_dtype": args.kv_cache_dtype})
         logger.info(f"[{why}] {ids if text is None else text!r}")
     if args.output_jsonl:
         with open(args.output_jsonl, "w", encoding="utf-8") as f:

@@ -13,6 +13,12 @@ The HIP decode kernels take bf16 / fp16 at head_dim 64 / 128. CPU tensors, fp32 
 GPU and other head dims run the torch math of :mod:`pyrecover_amd.ops.reference`
 (``attention_decode_ref`` / ``rope_append_ref``), noted once through ``_note_fallback`` like attention.
 
+``KVCache(kv_dtype="fp8")`` (``generate(kv_cache_dtype="fp8")``) keeps k / v as OCP e4m3fn bytes with one
+power-of-two scale per (token, kv head), about half the cache's memory and half the bytes a decode step
+reads: csrc/kernels/attention_decode_fp8.hip (``kv_quantize``, ``rope_append_fp8``, ``attn_decode_fp8``), the
+rule in ``ops/reference.py::kv_quantize_ref``. The prompt's attention stays unquantized; only what is stored
+is quantized. Opt-in: without it nothing changes.
+
 Sampling has two rules. ``sampler="torch"`` (the default) filters with ``torch.topk`` / ``torch.sort`` and
 draws with ``torch.multinomial`` from a seeded ``torch.Generator``. ``sampler="philox"`` is the stateless
 rule of csrc/kernels/sample.hip (:func:`sample_philox`): the uniform of a draw is a Philox function of
@@ -36,50 +42,101 @@ from .ops import reference as ref
 SYNC_EVERY = 16  # generate(): the finished mask is read back at most once per this many tokens
 
 
+KV_DTYPES = ("model", "fp8")
+
+
 class KVCache:
     """Per-layer k / v of shape [B, capacity, Hkv, D] (token-major, like every activation here) and the
-    int32 device tensor ``kv_len`` [B] of tokens held per sequence."""
+    int32 device tensor ``kv_len`` [B] of tokens held per sequence.
 
-    def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device):
+    ``kv_dtype="model"`` (the default) stores k / v in ``dtype``. ``kv_dtype="fp8"`` stores every head row
+    as D bytes of OCP e4m3fn (uint8 tensors ``k`` / ``v``) and one power-of-two fp32 scale (``k_scale`` /
+    ``v_scale`` [B, capacity, Hkv]) by the rule of ``ops/reference.py::kv_quantize_ref``: (D + 4) / (2 D)
+    of the 16-bit cache's bytes. ``dtype`` stays the model's dtype: the dtype of q and of the output."""
+
+    def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device,
+                 kv_dtype: str = "model"):
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"KVCache: kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         if capacity > model_args.seq_len:
             raise ValueError(f"KVCache capacity {capacity} exceeds the model's seq_len {model_args.seq_len} "
                              f"(the extent of the RoPE table)")
         if batch < 1 or capacity < 1:
             raise ValueError(f"KVCache needs batch >= 1 and capacity >= 1, got {batch}, {capacity}")
-        self.batch, self.capacity = batch, capacity
+        self.batch, self.capacity, self.dtype, self.kv_dtype = batch, capacity, dtype, kv_dtype
+        self.fp8 = kv_dtype == "fp8"
         shape = (model_args.n_layers, batch, capacity, model_args.kv_heads, model_args.head_dim)
-        self._k = torch.zeros(shape, dtype=dtype, device=device)
-        self._v = torch.zeros(shape, dtype=dtype, device=device)
+        self._k = torch.zeros(shape, dtype=torch.uint8 if self.fp8 else dtype, device=device)
+        self._v = torch.zeros_like(self._k)
         self.k = list(self._k.unbind(0))
         self.v = list(self._v.unbind(0))
+        n = model_args.n_layers
+        self.k_scale, self.v_scale = [None] * n, [None] * n
+        if self.fp8:  # an all-zero row has scale 1
+            self._k_scale = torch.ones(shape[:-1], dtype=torch.float32, device=device)
+            self._v_scale = torch.ones_like(self._k_scale)
+            self.k_scale = list(self._k_scale.unbind(0))
+            self.v_scale = list(self._v_scale.unbind(0))
         self.kv_len = torch.zeros(batch, dtype=torch.int32, device=device)
 
     def nbytes(self) -> int:
-        return 2 * self._k.numel() * self._k.element_size()
+        n = 2 * self._k.numel() * self._k.element_size()
+        return n + 2 * self._k_scale.numel() * 4 if self.fp8 else n
 
 
 def _decode_hip(qkv: torch.Tensor, head_dim: int) -> bool:
     return F._note_fallback("decode attention", qkv, _ext.hip16(qkv) and head_dim in (64, 128))
 
 
-def rope_append(qkv, tab, kv_len, k_cache, v_cache) -> None:
+def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None) -> None:
     """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D]: q rotated in place, rotated k and plain v into
-    cache row clamp(kv_len[b], 0, cap - 1). Bit-equal to ``rope_`` on the same row at that position."""
+    cache row clamp(kv_len[b], 0, cap - 1). Bit-equal to ``rope_`` on the same row at that position.
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows are quantized on the way in."""
+    fp8 = k_scale is not None
     if _decode_hip(qkv, k_cache.shape[-1]):
-        _ext.require_for(qkv).rope_append_(qkv, tab, kv_len, k_cache, v_cache)
+        C = _ext.require_for(qkv)
+        if fp8:
+            C.rope_append_fp8_(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
+        else:
+            C.rope_append_(qkv, tab, kv_len, k_cache, v_cache)
+    elif fp8:
+        ref.rope_append_fp8_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
     else:
         ref.rope_append_ref(qkv, tab, kv_len, k_cache, v_cache)
 
 
-def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None, k_scale=None,
+                     v_scale=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, Hq, D] over the caches [B, cap, Hkv, D]: sequence b attends to keys 0 .. kv_len[b] - 1.
-    Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path)."""
+    Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path).
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8) and the keys are their dequantized rows."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    fp8 = k_scale is not None
     if _decode_hip(q, q.shape[-1]):
-        o, lse = _ext.require_for(q).attn_decode(q, k_cache, v_cache, kv_len, scale)
+        C = _ext.require_for(q)
+        if fp8:
+            o, lse = C.attn_decode_fp8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+        else:
+            o, lse = C.attn_decode(q, k_cache, v_cache, kv_len, scale)
         return o, lse
-    o, lse = ref.attention_decode_ref(q, k_cache, v_cache, kv_len, scale)
+    if fp8:
+        o, lse = ref.attention_decode_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+    else:
+        o, lse = ref.attention_decode_ref(q, k_cache, v_cache, kv_len, scale)
     return o.to(q.dtype), lse
+
+
+def _store_prompt_kv(k, v, kc, vc, ks, vs) -> None:
+    """The k / v views [B, S, Hkv, D] of the fused QKV activation into cache rows 0 .. S - 1."""
+    S = k.shape[1]
+    if ks is None:
+        kc[:, :S].copy_(k)  # strided copies
+        vc[:, :S].copy_(v)
+    elif _decode_hip(k, k.shape[-1]):
+        _ext.require_for(k).kv_quantize_(k, v, kc, vc, ks, vs)
+    else:
+        kc[:, :S], ks[:, :S] = ref.kv_quantize_ref(k)
+        vc[:, :S], vs[:, :S] = ref.kv_quantize_ref(v)
 
 
 # ---------------------------------------------------------------------------------------
@@ -87,9 +144,10 @@ def _qkv_params(at):
     return [at.wq.weight, at.wk.weight, at.wv.weight]
 
 
-def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc):
+def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc, ks=None, vs=None):
     """The forward of ops/fused.py ``_AttentionBlock`` (same kernels, same rounding points), which also
-    leaves the rotated k and the plain v of positions 0 .. S - 1 in the cache."""
+    leaves the rotated k and the plain v of positions 0 .. S - 1 in the cache (quantized when the cache is
+    fp8; the attention itself runs on the unquantized k and v)."""
     a = model.model_args
     Hq, Hkv, D = a.n_heads, a.kv_heads, a.head_dim
     at = layer.attention
@@ -110,8 +168,7 @@ def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc):
     q = qkv[:, :nq].view(B, S, Hq, D)
     k = qkv[:, nq:nq + nk].view(B, S, Hkv, D)
     v = qkv[:, nq + nk:].view(B, S, Hkv, D)
-    kc[:, :S].copy_(k)  # strided copies of the k / v views of the fused QKV activation
-    vc[:, :S].copy_(v)
+    _store_prompt_kv(k, v, kc, vc, ks, vs)
     o, _ = F._attn_fwd(q, k, v, 1.0 / math.sqrt(D), True)
     return F._mm_nt(o.view(T, nq), w_o, "o").view(B, S, -1)
 
@@ -137,15 +194,25 @@ def _check_cache(model, cache: KVCache, B: int):
     if cache.batch != B or len(cache.k) != a.n_layers or tuple(cache.k[0].shape[2:]) != (a.kv_heads, a.head_dim):
         raise ValueError("KVCache does not match the model / batch")
     w = model.tok_embeddings.weight
-    if cache.k[0].dtype != w.dtype or cache.k[0].device != w.device:
-        raise ValueError(f"KVCache is {cache.k[0].dtype} on {cache.k[0].device}, the model {w.dtype} on {w.device}")
+    kind = getattr(cache, "fp8", False)
+    dtype = cache.dtype if kind else cache.k[0].dtype
+    if dtype != w.dtype or cache.k[0].device != w.device:
+        raise ValueError(f"KVCache is {dtype} on {cache.k[0].device}, the model {w.dtype} on {w.device}")
+    if kind and (cache.k[0].dtype != torch.uint8 or cache.k_scale[0] is None or
+                 tuple(cache.k_scale[0].shape) != tuple(cache.k[0].shape[:-1])):
+        raise ValueError("KVCache: an fp8 cache holds uint8 k / v and fp32 scales [B, capacity, Hkv]")
 
 
 @torch.no_grad()
 def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache) -> torch.Tensor:
     """tokens [B, S] (ragged prompts right-padded), lens [B] in 1 .. S -> logits [B, V] of row
     lens[b] - 1 of each sequence. Fills the cache rows 0 .. S - 1 and sets kv_len = lens. Causal
-    attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist."""
+    attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist.
+
+    With an fp8 cache the attention over the prompt still runs on the unquantized k / v; only what is
+    stored is quantized. The logits returned here, the first generated token's, are therefore bit-equal to
+    those of the ``"model"`` cache, and ``prefill(p)`` + ``decode_step(t)`` and ``prefill(p + t)`` see
+    different keys for the prompt: dequantized ones in the first, the 16-bit ones in the second."""
     B, S = tokens.shape
     _check_cache(model, cache, B)
     if S > cache.capacity:
@@ -159,7 +226,7 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache) -> 
             x, n1 = h, model._norm(layer.attention_norm, h, None)
         else:
             x, n1 = model._norm(layer.attention_norm, h, pending)
-        att = _prefill_attention(model, layer, n1, B, S, cache.k[i], cache.v[i])
+        att = _prefill_attention(model, layer, n1, B, S, cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i])
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
     cache.kv_len.copy_(lens.clamp(0, cache.capacity))
@@ -190,8 +257,9 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
             x, n1 = model._norm(layer.attention_norm, h, pending)
         at = layer.attention
         qkv = torch.mm(n1, model._weight(_qkv_params(at)).t())
-        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i])
-        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale)
+        ks, vs = cache.k_scale[i], cache.v_scale[i]  # None: a cache in the model's dtype
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs)
+        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale, ks, vs)
         att = F._mm_nt(o.view(B, nq), model._weight([at.wo.weight]), "o")
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
@@ -357,8 +425,8 @@ def _graph_refusal(model, device, dtype, sampler: str, temperature: float, use_c
 @torch.no_grad()
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
-             stats: Optional[Dict] = None, sampler: str = "torch",
-             graph: bool = False) -> Tuple[List[List[int]], List[str]]:
+             stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
+             kv_cache_dtype: str = "model") -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -376,11 +444,21 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     bookkeeping are one kernel launch per token (:class:`DeviceSampler`). ``graph=True`` also replays
     sample -> ``decode_step`` as a hipGraph (:class:`DecodeGraph`); it needs ``sampler="philox"`` or
     temperature 0 and a bf16 / fp16 GPU model on the HIP decode path, and raises ``ValueError`` with the
-    reason otherwise."""
+    reason otherwise.
+
+    ``kv_cache_dtype="fp8"`` keeps the cache as e4m3fn bytes with one power-of-two scale per (token, kv
+    head) (:class:`KVCache`): about half the cache memory and half the bytes a decode step reads. The
+    prompt's attention runs unquantized (:func:`prefill`), so the first generated token is the one the
+    ``"model"`` cache gives; later tokens attend to dequantized keys and values. It needs the cache:
+    ``use_cache=False`` raises ``ValueError``."""
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
     if sampler not in ("torch", "philox"):
         raise ValueError(f"generate: sampler must be 'torch' or 'philox', got {sampler!r}")
+    if kv_cache_dtype not in KV_DTYPES:
+        raise ValueError(f"generate: kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
+    if kv_cache_dtype != "model" and not use_cache:
+        raise ValueError(f"generate: kv_cache_dtype={kv_cache_dtype!r} needs the KV cache (use_cache=True)")
     device, dtype = _model_device_dtype(model)
     if graph:
         why = _graph_refusal(model, device, dtype, sampler, temperature, use_cache)
@@ -411,7 +489,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     timer = _Timer(device)
     timer.mark()
     if use_cache:
-        cache = KVCache(args, B, cap, dtype, device)
+        cache = KVCache(args, B, cap, dtype, device, kv_cache_dtype)
         logits = prefill(model, buf[:, :S], lens, cache)
     else:
         bi = torch.arange(B, device=device)

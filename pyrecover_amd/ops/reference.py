@@ -233,8 +233,14 @@ def rope_append_ref(qkv, tab, kv_len, k_cache, v_cache) -> None:
     """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D] at positions pos[b] = clamp(kv_len[b], 0, cap - 1):
     q is rotated in place, the rotated k and the plain v are written into row pos[b] of the caches
     (RoPE math of :func:`rope_inplace_2d`: opmath rotation from table row pos[b], one rounding)."""
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape[1:])
+    k_cache[bi, pos] = k
+    v_cache[bi, pos] = v
+
+
+def _rope_new_rows(qkv, tab, kv_len, cap: int, Hkv: int, D: int):
+    """Rotates q in place; returns (batch index, pos, rotated k [B, Hkv, D] in qkv's dtype, v [B, Hkv, D])."""
     B = qkv.shape[0]
-    cap, Hkv, D = k_cache.shape[1:]
     nk = Hkv * D
     nq = qkv.shape[1] - 2 * nk
     pos = kv_len.to(device=qkv.device, dtype=torch.long).clamp(0, cap - 1)
@@ -244,9 +250,46 @@ def rope_append_ref(qkv, tab, kv_len, k_cache, v_cache) -> None:
     a, b = x[..., 0], x[..., 1]
     rot = torch.stack([a * c - b * s, a * s + b * c], dim=-1).reshape(B, nq + nk).to(qkv.dtype)
     qkv[:, :nq] = rot[:, :nq]
-    bi = torch.arange(B, device=qkv.device)
-    k_cache[bi, pos] = rot[:, nq:].view(B, Hkv, D)
-    v_cache[bi, pos] = qkv[:, nq + nk:].view(B, Hkv, D)
+    return torch.arange(B, device=qkv.device), pos, rot[:, nq:].view(B, Hkv, D), qkv[:, nq + nk:].view(B, Hkv, D)
+
+
+# ---------------------------------------------------------------------------------------
+# fp8 KV cache (HIP: csrc/kernels/attention_decode_fp8.hip). A cache row, the D values of one (sequence,
+# position, kv head), is D bytes of OCP e4m3fn (held as uint8) and one fp32 scale 2^e.
+
+def kv_quantize_ref(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., D] -> (bytes uint8 [..., D], scale fp32 [...]) by the cache's rule, on x cast to fp32 (exact
+    for bf16 / fp16): amax = max |x_i|; amax == 0 gives scale 1 and bytes 0; otherwise (m, k) = frexp(amax)
+    and e = clamp(k - 9 + (m > 0.875), -126, 127), the smallest e with amax * 2^-e <= 448; scale = 2^e and
+    byte_i = e4m3fn_rne(x_i * 2^-e). The product is exact, so there is one rounding and no saturation."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    m, k = torch.frexp(amax)
+    e = (k.to(torch.int32) - 9 + (m > 0.875).to(torch.int32)).clamp(-126, 127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    y = torch.ldexp(xf, -e.unsqueeze(-1)).masked_fill((amax == 0).unsqueeze(-1), 0.0)  # -0.0 rows: bytes 0 too
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), torch.ldexp(torch.ones_like(amax), e)
+
+
+def kv_dequantize_ref(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """bytes [..., D], scale [...] -> byte_i * scale in ``dtype``: exact in fp32, bf16 and fp16."""
+    return (q.view(torch.float8_e4m3fn).to(torch.float32) * scale.unsqueeze(-1)).to(dtype)
+
+
+def rope_append_fp8_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale) -> None:
+    """:func:`rope_append_ref` over an fp8 cache: q is rotated in place as there; the k row is rotated in
+    opmath, rounded once to qkv's dtype and then quantized, the v row quantized from its values: the cache
+    is a pure function of what the 16-bit cache would hold."""
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape[1:])
+    k_cache[bi, pos], k_scale[bi, pos] = kv_quantize_ref(k)
+    v_cache[bi, pos], v_scale[bi, pos] = kv_quantize_ref(v)
+
+
+def attention_decode_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale: Optional[float] = None):
+    """:func:`attention_decode_ref` on the dequantized cache, in q's precision promoted to at least fp32."""
+    dt = up(q).dtype
+    return attention_decode_ref(q, kv_dequantize_ref(k_cache, k_scale, dt), kv_dequantize_ref(v_cache, v_scale, dt),
+                                kv_len, scale)
 
 
 # ---------------------------------------------------------------------------------------

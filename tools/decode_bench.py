@@ -12,6 +12,11 @@ Every timed call reads another layer's cache (as a decode step does), and the la
     python tools/decode_bench.py [--layers 4] [--iters 50] [--skip-step] [--shapes 7b,llama3-8b]
     python tools/decode_bench.py --shapes 7b --sampler both --graph     # whole tokens: sample + bookkeeping + step
     python tools/decode_bench.py --sample-bench                         # the sampler alone
+    python tools/decode_bench.py --kv-cache-dtype both                  # the fp8 cache beside the 16-bit one
+
+``--kv-cache-dtype model|fp8|both`` picks the cache of every table: ``fp8`` is the e4m3fn cache with one
+power-of-two scale per (token, kv head) (``attn_decode_fp8``; its K/V rate counts the bytes it reads, scales
+included), ``both`` measures the two arms in one process on the same q and the same K / V values.
 
 ``--sampler torch|philox|both`` times whole generated tokens (sampling, the bookkeeping of ``generate`` and the
 decode step) per arm: ``torch`` is generate()'s default loop (``sample_token`` with a ``torch.Generator`` and
@@ -57,16 +62,36 @@ def timed_us(fn, iters, warmup=5):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def bench_attention(name, cfg, B, ctx, iters, dev):
+def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
     C = _ext.native()
     Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
     per_layer = 2 * B * ctx * Hkv * D * 2  # bytes of K and V one call reads
-    n_buf = max(2, -(-2 * L3_BYTES // per_layer))  # rotate over >= 2 x the Infinity Cache
+    per_layer8 = 2 * B * ctx * Hkv * (D + 4)  # ... from an fp8 cache: bytes and scales
+    # rotate over >= 2 x the Infinity Cache (of the smaller arm's bytes)
+    n_buf = max(2, -(-2 * L3_BYTES // (per_layer8 if "fp8" in kinds else per_layer)))
     ks = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
     vs = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
     q = torch.randn(B, Hq, D, device=dev).bfloat16()
     n = torch.full((B,), ctx, device=dev, dtype=torch.int32)
     scale = 1 / math.sqrt(D)
+    hip8 = None
+    if "fp8" in kinds:
+        c8 = []
+        for k, v in zip(ks, vs):
+            kq, vq = torch.empty_like(k, dtype=torch.uint8), torch.empty_like(v, dtype=torch.uint8)
+            sk, sv = (torch.empty(B, ctx, Hkv, device=dev) for _ in range(2))
+            C.kv_quantize_(k, v, kq, vq, sk, sv)
+            c8.append((kq, vq, sk, sv))
+        hip8 = timed_us(lambda i: C.attn_decode_fp8(q, *c8[i % n_buf], n, scale), iters)
+        o8, _ = C.attn_decode_fp8(q, *c8[0], n, scale)
+        kd, vd = (ref.kv_dequantize_ref(c8[0][j], c8[0][j + 2]) for j in (0, 1))
+        err8 = (o8.float() - ref.attention_decode_ref(q, kd, vd, n, scale)[0]).abs().max().item()
+        del kd, vd
+    if "model" not in kinds:
+        print(f"{name}: attn_decode_fp8 B={B} ctx={ctx} Hq/Hkv={Hq}/{Hkv} D={D} KC={C.attn_decode_fp8_chunk()} "
+              f"({per_layer8 / 2**20:.0f} MiB of K/V bytes and scales per call, {n_buf} caches in rotation)")
+        print(f"  HIP fp8 {hip8:7.1f} us  {per_layer8 / hip8 / 1e6:6.2f} TB/s   (max |o - o_ref(dequantized)| {err8:.2e})")
+        return hip8, None
     hip = timed_us(lambda i: C.attn_decode(q, ks[i % n_buf], vs[i % n_buf], n, scale), iters)
     tor = timed_us(lambda i: ref.attention_decode_ref(q, ks[i % n_buf], vs[i % n_buf], n, scale), max(5, iters // 5), 2)
     o, _ = C.attn_decode(q, ks[0], vs[0], n, scale)
@@ -76,10 +101,27 @@ def bench_attention(name, cfg, B, ctx, iters, dev):
           f"({per_layer / 2**20:.0f} MiB of K/V per call, {n_buf} caches in rotation)")
     print(f"  HIP   {hip:9.1f} us  {per_layer / hip / 1e6:6.2f} TB/s")
     print(f"  torch {tor:9.1f} us  {per_layer / tor / 1e6:6.2f} TB/s   (HIP is {tor / hip:.1f}x; max |o - o_ref| {err:.2e})")
+    if hip8 is not None:
+        print(f"  HIP fp8 {hip8:7.1f} us  {per_layer8 / hip8 / 1e6:6.2f} TB/s of {per_layer8 / 2**20:.0f} MiB (bytes and scales; "
+              f"KC={C.attn_decode_fp8_chunk()}): {hip / hip8:.2f}x of the 16-bit call; "
+              f"max |o - o_ref(dequantized)| {err8:.2e}")
     return hip, tor
 
 
-def bench_step(name, preset, B, ctx, layers, iters, dev):
+def filled_cache(cfg, B, ctx, dev, kv_dtype):
+    """A full cache of standard normal K / V (quantized from them when fp8)."""
+    cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev, kv_dtype=kv_dtype)
+    for i, (k, v) in enumerate(zip(cache.k, cache.v)):
+        if cache.fp8:
+            src = torch.randn(2, B, ctx, cfg.kv_heads, cfg.head_dim, device=dev).bfloat16()
+            _ext.native().kv_quantize_(src[0], src[1], k, v, cache.k_scale[i], cache.v_scale[i])
+        else:
+            k.normal_()
+            v.normal_()
+    return cache
+
+
+def bench_step(name, preset, B, ctx, layers, iters, dev, kv_dtype="model"):
     cfg = get_preset(preset, n_layers=layers, seq_len=ctx)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
@@ -88,10 +130,7 @@ def bench_step(name, preset, B, ctx, layers, iters, dev):
     torch.set_default_dtype(prev)
     model.eval()
     model.flatten_(shadows=False)
-    cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev)
-    for k, v in zip(cache.k, cache.v):
-        k.normal_()
-        v.normal_()
+    cache = filled_cache(cfg, B, ctx, dev, kv_dtype)
     tok = torch.randint(0, cfg.vocab_size, (B,), device=dev)
 
     def step(_):
@@ -100,7 +139,8 @@ def bench_step(name, preset, B, ctx, layers, iters, dev):
 
     us = timed_us(step, iters)
     kv = cache.nbytes()
-    print(f"{name}: decode_step, {layers} layers, B={B} ctx={ctx}: {us:9.1f} us ({us / layers:.1f} us per layer; "
+    print(f"{name}: decode_step, {kv_dtype} cache ({kv / 2**20:.0f} MiB), {layers} layers, B={B} ctx={ctx}: "
+          f"{us:9.1f} us ({us / layers:.1f} us per layer; "
           f"K/V read {kv / us / 1e6:.2f} TB/s of step time)")
     return us
 
@@ -108,7 +148,7 @@ def bench_step(name, preset, B, ctx, layers, iters, dev):
 SAMPLING = dict(temperature=0.8, top_k=50, top_p=0.95)
 
 
-def bench_tokens(name, preset, B, ctx, layers, iters, dev, samplers, graph):
+def bench_tokens(name, preset, B, ctx, layers, iters, dev, samplers, graph, kv_dtype="model"):
     cfg = get_preset(preset, n_layers=layers, seq_len=ctx)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
@@ -117,10 +157,7 @@ def bench_tokens(name, preset, B, ctx, layers, iters, dev, samplers, graph):
     torch.set_default_dtype(prev)
     model.eval()
     model.flatten_(shadows=False)
-    cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev)
-    for k, v in zip(cache.k, cache.v):
-        k.normal_()
-        v.normal_()
+    cache = filled_cache(cfg, B, ctx, dev, kv_dtype)
     warmup = 8
     total = warmup + iters
     start = ctx - total - 2  # the timed tokens end on a nearly full cache and never fill it
@@ -164,8 +201,8 @@ def bench_tokens(name, preset, B, ctx, layers, iters, dev, samplers, graph):
         dg = inf.DecodeGraph(model, cache, fresh_logits(), ds)
         results["graph + philox"] = timed_us(lambda _: dg.step(), iters, warmup)
         assert dg.captured
-    print(f"{name}: one generated token (sample + bookkeeping + decode_step), {layers} layers, B={B} ctx={ctx}, "
-          f"V={cfg.vocab_size}")
+    print(f"{name}: one generated token (sample + bookkeeping + decode_step), {kv_dtype} cache, {layers} layers, B={B} "
+          f"ctx={ctx}, V={cfg.vocab_size}")
     base = results.get("eager + torch")
     for arm, us in results.items():
         rel = f"  ({base / us:.2f}x of eager + torch)" if base and arm != "eager + torch" else ""
@@ -203,8 +240,11 @@ def main():
                     help="time whole generated tokens with this sampler instead of the kernel / step tables")
     ap.add_argument("--graph", action="store_true", help="add the hipGraph-replayed philox arm (DecodeGraph)")
     ap.add_argument("--sample-bench", action="store_true", help="time the sampler alone")
+    ap.add_argument("--kv-cache-dtype", choices=("model", "fp8", "both"), default="model",
+                    help="the cache of every table: the model's dtype, fp8 (e4m3fn bytes + scales), or both arms")
     a = ap.parse_args()
     shapes = [s for s in SHAPES if s[0] in a.shapes.split(",")]
+    kinds = ("model", "fp8") if a.kv_cache_dtype == "both" else (a.kv_cache_dtype,)
     dev = torch.device("cuda", 0)
     _ext.native()
     if a.sample_bench:
@@ -213,13 +253,15 @@ def main():
     if a.sampler or a.graph:
         samplers = ("torch", "philox") if a.sampler == "both" else (a.sampler,) if a.sampler else ()
         for name, preset, B, ctx in shapes:
-            bench_tokens(name, preset, B, ctx, a.layers, a.iters, dev, samplers, a.graph)
+            for kind in kinds:
+                bench_tokens(name, preset, B, ctx, a.layers, a.iters, dev, samplers, a.graph, kind)
         return
     for name, preset, B, ctx in shapes:
-        bench_attention(name, get_preset(preset), B, ctx, a.iters, dev)
+        bench_attention(name, get_preset(preset), B, ctx, a.iters, dev, kinds)
     if not a.skip_step:
         for name, preset, B, ctx in shapes:
-            bench_step(name, preset, B, ctx, a.layers, max(10, a.iters // 2), dev)
+            for kind in kinds:
+                bench_step(name, preset, B, ctx, a.layers, max(10, a.iters // 2), dev, kind)
 
 
 if __name__ == "__main__":
