@@ -968,16 +968,20 @@ void check_decode_common(const at::Tensor& ref, const at::Tensor& kc, const at::
               op, ": kv_len must be contiguous int32 [B]");
 }
 
-// qkv [B, (Hq + 2 Hkv) D] (rows of the fused QKV activation): q rotated in place at position
-// clamp(kv_len[b], 0, cap - 1), rotated k and plain v written into that row of the caches.
+// qkv [B * T, (Hq + 2 Hkv) D] (rows of the fused QKV activation, T new tokens per sequence, B the caches'):
+// row b * T + t has q rotated in place at position kv_len[b] + t, rotated k and plain v written into that
+// row of the caches. T = 1 clamps the row to cap - 1; T > 1 stores nothing for a position >= cap.
 void rope_append_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_len, at::Tensor k_cache,
                   at::Tensor v_cache) {
   const Range range_("pyrecover::rope_append");
   check_dev(qkv, "qkv");
   check_row_major(qkv, "rope_append qkv");
-  const int64_t B = qkv.size(0);
+  const int64_t B = k_cache.dim() == 4 ? k_cache.size(0) : qkv.size(0);
   check_decode_common(qkv, k_cache, v_cache, kv_len, B, "rope_append");
   const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2), D = k_cache.size(3);
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) % B == 0 && qkv.size(0) / B <= (int64_t)INT32_MAX / 2,
+              "rope_append: qkv must hold T rows for each of the caches' B = ", B, " sequences, got ", qkv.sizes());
+  const int64_t T = qkv.size(0) / B;
   TORCH_CHECK(qkv.size(1) % D == 0 && qkv.size(1) / D > 2 * Hkv && (qkv.size(1) / D - 2 * Hkv) % Hkv == 0,
               "rope_append: qkv must be [B, (Hq + 2 Hkv) D] with Hq a multiple of Hkv, got ", qkv.sizes());
   TORCH_CHECK(qkv.stride(0) % 8 == 0, "rope_append: the qkv row stride must be a multiple of 8 elements");
@@ -988,8 +992,40 @@ void rope_append_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_le
               "rope_append: table must be contiguous fp32 [>= cap, D/2, 2]");
   const c10::DeviceGuard guard(qkv.device());
   check(pra_rope_append(dt(qkv), qkv.data_ptr(), tab.data_ptr(), kv_len.data_ptr<int>(), k_cache.data_ptr(),
-                        v_cache.data_ptr(), (int)B, qkv.stride(0), (int)Hq, (int)Hkv, (int)D, (int)cap, stream_of(qkv)),
+                        v_cache.data_ptr(), (int)B, (int)T, qkv.stride(0), (int)Hq, (int)Hkv, (int)D, (int)cap,
+                        stream_of(qkv)),
         "rope_append");
+}
+
+// q [B, T, Hq, D] (token rows may be strided views of the QKV activation), caches [B, cap, Hkv, D] that hold
+// the T new tokens already, kv_len int32 [B] on the device (tokens held before this append)
+// -> (o [B, T, Hq, D], lse fp32 [B, T, Hq]). Query t attends to keys 0 .. min(kv_len[b] + t, cap - 1).
+std::vector<at::Tensor> attn_extend(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                    const at::Tensor& kv_len, double scale) {
+  const Range range_("pyrecover::attn_extend");
+  check_dev(q, "q");
+  TORCH_CHECK(q.dim() == 4 && q.size(1) > 0, "attn_extend: q must be [B, T, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  check_decode_common(q, k_cache, v_cache, kv_len, B, "attn_extend");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "attn_extend: q and the caches disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_extend: n_heads must be a multiple of n_kv_heads");
+  TORCH_CHECK(T * (Hq / Hkv) <= (int64_t)INT32_MAX / 2, "attn_extend: bad shape");
+  // rows of one token contiguous, tokens at one stride across the batch: else a packed copy
+  int64_t ldq = T > 1 ? q.stride(1) : B > 1 ? q.stride(0) : Hq * D;  // a dim of size 1 has no stride to speak of
+  const bool view_ok = q.stride(3) == 1 && q.stride(2) == D && ldq % 8 == 0 && ldq >= Hq * D &&
+                       (B == 1 || q.stride(0) == T * ldq);
+  at::Tensor qc = view_ok ? q : q.contiguous();
+  if (!view_ok) ldq = Hq * D;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_extend: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, T, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, T, Hq}, q.options().dtype(at::kFloat));
+  check(pra_attn_extend(dt(q), qc.data_ptr(), ldq, k_cache.data_ptr(), v_cache.data_ptr(),
+                        kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)Hq, (int)Hkv,
+                        (int)D, (int)cap, (float)scale, stream_of(q)),
+        "attn_extend");
+  return {o, lse};
 }
 
 // q [B, Hq, D] (rows may be strided views of the QKV activation), caches [B, cap, Hkv, D], kv_len int32 [B]
@@ -1344,6 +1380,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
         py::arg("scale"));
   m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
+  m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
+        py::arg("scale"));
   m.def("kv_quantize_", &kv_quantize_, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("k_scale"), py::arg("v_scale"));
   m.def("rope_append_fp8_", &rope_append_fp8_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_cache"),

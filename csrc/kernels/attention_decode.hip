@@ -4,9 +4,12 @@
 // here. kv_len is int32 [B] ON THE DEVICE: no launch argument depends on a host copy of it, so a decode
 // step never synchronises.
 //
-//   rope_append  the new token's fused QKV row: q rotated in place, rotated k and plain v written
-//                into cache row pos[b] = clamp(kv_len[b], 0, cap - 1). The rotation is rope_kernel's
-//                (elementwise.hip): same table, rot_pair in fp32, one rounding -- bit-equal to it.
+//   rope_append  the fused QKV rows of T new tokens per sequence (row b * T + t at position
+//                p = kv_len[b] + t): q rotated in place, rotated k and plain v written into cache row p.
+//                The rotation is rope_kernel's (elementwise.hip): same table, rot_pair in fp32, one
+//                rounding -- bit-equal to it. T = 1 (a decode step) clamps the row into the cache:
+//                pos[b] = clamp(kv_len[b], 0, cap - 1). With T > 1 (attention_extend.hip) a row with
+//                p >= cap stores nothing and its q is rotated with table row cap - 1.
 //   attn_decode  one query per sequence over keys 0 .. kv_len[b] - 1. The kernel streams K and V once
 //                (about Hq/Hkv flop per byte: the target is bytes per second), so the cache rows go
 //                straight to VGPRs as 16-B loads, all of a chunk's in flight at once, and the dot
@@ -44,25 +47,28 @@ __device__ __forceinline__ void dec_rot_pair(float a, float b, float c, float s,
   o1 = __builtin_fmaf(a, s, b * c);
 }
 
-// qkv [B][ld]: q (Hq heads) | k (Hkv) | v (Hkv), D columns each. One lane per 8 columns.
+// qkv [B * nt][ld]: q (Hq heads) | k (Hkv) | v (Hkv), D columns each. One lane per 8 columns.
 template <typename T>
 __global__ __launch_bounds__(256) void rope_append_kernel(T* __restrict__ qkv, const float2* __restrict__ tab,
                                                           const int* __restrict__ kv_len, T* __restrict__ kc,
-                                                          T* __restrict__ vc, int B, long ld, int Hq, int Hkv, int D,
-                                                          int cap) {
+                                                          T* __restrict__ vc, int B, int nt, long ld, int Hq, int Hkv,
+                                                          int D, int cap) {
   const int nq = Hq * D, nk = Hkv * D;
   const int vpr = (nq + 2 * nk) / 8;
-  const long total = (long)B * vpr;
+  const long total = (long)B * nt * vpr;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-    const int b = (int)(idx / vpr);
-    const int col = (int)(idx - (long)b * vpr) * 8;
-    const int pos = min(max(kv_len[b], 0), cap - 1);
-    T* p = qkv + (long)b * ld + col;
+    const long r = idx / vpr;  // row b * nt + t
+    const int b = (int)(r / nt);
+    const int col = (int)(idx - r * vpr) * 8;
+    const int at = min(max(kv_len[b], 0), cap) + (int)(r - (long)b * nt);  // <= cap + nt - 1
+    const int pos = min(at, cap - 1);
+    const bool keep = at < cap || nt == 1;  // one token: the clamped row is overwritten
+    T* p = qkv + r * ld + col;
     float v[8];
     load8<T>(p, v);
     const long row = ((long)b * cap + pos) * nk;  // cache row of this token, in elements
     if (col >= nq + nk) {
-      store8<T>(vc + row + (col - nq - nk), v);  // exact copy
+      if (keep) store8<T>(vc + row + (col - nq - nk), v);  // exact copy
       continue;
     }
     const int pi = (col % D) / 2;
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(256) void rope_append_kernel(T* __restrict__ qkv, c
     for (int k = 0; k < 4; ++k) dec_rot_pair(v[2 * k], v[2 * k + 1], c[k], s[k], o[2 * k], o[2 * k + 1]);
     if (col < nq)
       store8<T>(p, o);
-    else
+    else if (keep)
       store8<T>(kc + row + (col - nq), o);
   }
 }
@@ -355,14 +361,16 @@ long pra_attn_decode_ws_floats(int B, int Hq, int D, int cap) {
 }
 
 hipError_t pra_rope_append(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
-                           int B, long ld, int Hq, int Hkv, int D, int cap, hipStream_t s) {
-  if (B <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || D % 8 || ld % 8) return hipErrorInvalidValue;
-  const long items = (long)B * (Hq + 2 * Hkv) * D / 8;
+                           int B, int nt, long ld, int Hq, int Hkv, int D, int cap, hipStream_t s) {
+  if (B <= 0 || nt <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || D % 8 || ld % 8 || (long)cap + nt > 0x7fffffffL)
+    return hipErrorInvalidValue;
+  const long items = (long)B * nt * (Hq + 2 * Hkv) * D / 8;
   long grid = (items + 255) / 256;
   if (grid > 2048) grid = 2048;
   PRA_DISPATCH_16BIT(dtype, T,
                      hipLaunchKernelGGL((pra::rope_append_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s, (T*)qkv,
-                                        (const float2*)tab, kv_len, (T*)k_cache, (T*)v_cache, B, ld, Hq, Hkv, D, cap));
+                                        (const float2*)tab, kv_len, (T*)k_cache, (T*)v_cache, B, nt, ld, Hq, Hkv, D,
+                                        cap));
   return hipGetLastError();
 }
 

@@ -176,10 +176,12 @@ void pra_attn_set_options(const pra_attn_options* in);
 
 // KV-cache generation (attention_decode.hip), bf16 / fp16. Caches are [B][cap][Hkv][D] contiguous;
 // kv_len is int32 [B] on the device and is clamped by the kernels (no host copy is ever read).
-// rope_append: qkv [B][ld] = q | k | v of the new tokens; rotates q in place, writes rotated k and
-// plain v into cache row clamp(kv_len[b], 0, cap - 1). tab: float2 [>= cap][D/2].
+// rope_append: qkv [B * nt][ld] = q | k | v of nt new tokens per sequence, row b * nt + t at position
+// p = clamp(kv_len[b], 0, cap) + t; rotates q in place, writes rotated k and plain v into cache row p.
+// nt == 1: the row is clamp(kv_len[b], 0, cap - 1). nt > 1: a row with p >= cap stores nothing and its q
+// is rotated with table row cap - 1. tab: float2 [>= cap][D/2].
 hipError_t pra_rope_append(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
-                           int B, long ld, int Hq, int Hkv, int D, int cap, hipStream_t s);
+                           int B, int nt, long ld, int Hq, int Hkv, int D, int cap, hipStream_t s);
 // q, o [B][Hq][D] contiguous, lse fp32 [B][Hq]; sequence b attends to keys 0 .. clamp(kv_len[b], 0, cap) - 1.
 // D 64 or 128. ws: pra_attn_decode_ws_floats fp32 words. pra_attn_decode_chunk: keys per chunk.
 hipError_t pra_attn_decode(int dtype, const void* q, const void* k_cache, const void* v_cache, const int* kv_len,
@@ -190,6 +192,14 @@ int pra_attn_decode_chunk();
 // the merge of pra_attn_decode alone: ws_o [B][Hq][NC][D], ws_ml [B][Hq][NC][2], NC = ceil(cap / chunk)
 hipError_t pra_attn_decode_combine(int dtype, const float* ws_o, const float* ws_ml, const int* kv_len, void* o,
                                    float* lse, int B, int Hq, int D, int cap, int NC, hipStream_t s);
+
+// Multi-token append (attention_extend.hip), bf16 / fp16, D 64 or 128. q: T queries per sequence, row
+// b * T + t of a [B * T][ldq] view (Hq * D columns, ldq % 8 == 0); query t of sequence b attends to keys
+// 0 .. min(clamp(kv_len[b], 0, cap) + t, cap - 1) of the caches, which hold the new tokens' k / v already
+// (pra_rope_append with nt = T runs first). o [B][T][Hq][D] contiguous, lse fp32 [B][T][Hq].
+hipError_t pra_attn_extend(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
+                           const int* kv_len, void* o, float* lse, int B, int T, int Hq, int Hkv, int D, int cap,
+                           float scale, hipStream_t s);
 
 // fp8 KV cache (attention_decode_fp8.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D] of
 // e4m3fn bytes, k_scale, v_scale fp32 [B][cap][Hkv], powers of two. dtype is the 16-bit type of qkv / q / o.

@@ -2,7 +2,7 @@
 
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
         --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
-        [--sampler philox --decode-graph] [--kv-cache-dtype fp8]
+        [--sampler philox --decode-graph] [--kv-cache-dtype fp8] [--prefill-chunk 512]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
 ``--model-dtype``, ``--tokenizer-name-or-path``) and the checkpoint flags (``--checkpoint-dir``,
@@ -75,6 +75,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="model: the cache holds k / v in the model's dtype. fp8: e4m3fn bytes with one "
                         "power-of-two scale per (token, kv head), about half the cache memory; the prompt's "
                         "attention stays unquantized, so the first generated token does not change")
+    p.add_argument("--prefill-chunk", type=int, default=0, metavar="N",
+                   help="feed the prompt through in pieces of N tokens, each appended to the cache so far "
+                        "(csrc/kernels/attention_extend.hip): the prefill's activation memory scales with N, not "
+                        "with the prompt. 0 (default): one pass over the whole prompt. Not with --kv-cache-dtype fp8")
     p.add_argument("--no-kv-cache", action="store_true",
                    help="naive path: a full forward over the whole prefix per new token (debugging aid)")
     p.add_argument("--output-jsonl", type=str, default=None,
@@ -109,14 +113,14 @@ def main(argv=None) -> int:
     tokens, reasons = generate(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                top_p=args.top_p, seed=args.seed, eos_id=eos, use_cache=not args.no_kv_cache,
                                stats=stats, sampler=args.sampler, graph=args.decode_graph,
-                               kv_cache_dtype=args.kv_cache_dtype)
+                               kv_cache_dtype=args.kv_cache_dtype, prefill_chunk=args.prefill_chunk)
     records = []
     for p, ids, why in zip(prompts, tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None
         records.append({"prompt_ids": list(p), "generated_ids": ids, "text": text, "finish_reason": why,
                         "prefill_ms": stats["prefill_ms"], "decode_ms_per_token": stats["decode_ms_per_token"],
                         "checkpoint_step": step, "sampler": args.sampler, "decode_graph": args.decode_graph,
-                        "kv_cache_dtype": args.kv_cache_dtype})
+                        "kv_cache_dtype": args.kv_cache_dtype, "prefill_chunks": stats["prefill_chunks"]})
         logger.info(f"[{why}] {ids if text is None else text!r}")
     if args.output_jsonl:
         with open(args.output_jsonl, "w", encoding="utf-8") as f:

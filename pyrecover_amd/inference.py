@@ -9,9 +9,16 @@ per sequence through all layers on the two kernels of csrc/kernels/attention_dec
 ``attn_decode`` (one query per sequence over the cache). ``kv_len`` lives on the device and no kernel
 argument depends on a host copy of it: a decode step never synchronises.
 
+``extend`` appends T > 1 tokens per sequence to a cache that already holds keys (a follow-up turn, a
+continuation after a shared prefix, a scoring or verification pass): the T-token ``rope_append`` and
+``attn_extend`` of csrc/kernels/attention_extend.hip (T queries per sequence over keys 0 .. kv_len[b] + t).
+``prefill(chunk=N)`` feeds a prompt through it in pieces of N columns, so the prefill's activation memory
+is bounded by the piece. fp8 caches are refused by both.
+
 The HIP decode kernels take bf16 / fp16 at head_dim 64 / 128. CPU tensors, fp32 / fp64 models on the
 GPU and other head dims run the torch math of :mod:`pyrecover_amd.ops.reference`
-(``attention_decode_ref`` / ``rope_append_ref``), noted once through ``_note_fallback`` like attention.
+(``attention_decode_ref`` / ``attention_extend_ref`` / ``rope_append_ref``), noted once through
+``_note_fallback`` like attention.
 
 ``KVCache(kv_dtype="fp8")`` (``generate(kv_cache_dtype="fp8")``) keeps k / v as OCP e4m3fn bytes with one
 power-of-two scale per (token, kv head), about half the cache's memory and half the bytes a decode step
@@ -89,10 +96,15 @@ def _decode_hip(qkv: torch.Tensor, head_dim: int) -> bool:
 
 
 def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None) -> None:
-    """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D]: q rotated in place, rotated k and plain v into
-    cache row clamp(kv_len[b], 0, cap - 1). Bit-equal to ``rope_`` on the same row at that position.
-    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows are quantized on the way in."""
+    """The new tokens' fused QKV rows [B * T, (Hq + 2 Hkv) D], T per sequence (B is the caches'): row
+    b * T + t has q rotated in place at position kv_len[b] + t, rotated k and plain v into that cache row.
+    Bit-equal to ``rope_`` on the same row at that position. T = 1 clamps the row to cap - 1; with T > 1 a
+    position at or beyond the capacity stores nothing (its q takes table row cap - 1).
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows are quantized on the way in
+    (T = 1 only)."""
     fp8 = k_scale is not None
+    if fp8 and qkv.shape[0] != k_cache.shape[0]:
+        raise ValueError("rope_append: an fp8 cache takes one token per sequence (extend does not serve fp8 caches)")
     if _decode_hip(qkv, k_cache.shape[-1]):
         C = _ext.require_for(qkv)
         if fp8:
@@ -123,6 +135,19 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
         o, lse = ref.attention_decode_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
     else:
         o, lse = ref.attention_decode_ref(q, k_cache, v_cache, kv_len, scale)
+    return o.to(q.dtype), lse
+
+
+def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """q [B, T, Hq, D] over the caches [B, cap, Hkv, D], which hold the T new tokens' k / v already
+    (:func:`rope_append` first); ``kv_len`` [B] counts the tokens held before the append. Query t of
+    sequence b attends to keys 0 .. min(kv_len[b] + t, cap - 1). Returns (o [B, T, Hq, D] in q's dtype,
+    lse fp32 [B, T, Hq] -- the opmath dtype on the torch path)."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if _decode_hip(q, q.shape[-1]):
+        o, lse = _ext.require_for(q).attn_extend(q, k_cache, v_cache, kv_len, scale)
+        return o, lse
+    o, lse = ref.attention_extend_ref(q, k_cache, v_cache, kv_len, scale)
     return o.to(q.dtype), lse
 
 
@@ -203,8 +228,92 @@ def _check_cache(model, cache: KVCache, B: int):
         raise ValueError("KVCache: an fp8 cache holds uint8 k / v and fp32 scales [B, capacity, Hkv]")
 
 
+def _refuse_fp8(cache: KVCache, what: str) -> None:
+    if getattr(cache, "fp8", False):
+        raise ValueError(f"{what} does not serve an fp8 KV cache: the prompt's attention is defined as unquantized "
+                         f"(prefill), and new tokens attending to their own dequantized keys would change that")
+
+
+def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
+    """tokens [B, T] through every layer as an append at ``cache.kv_len`` (left unchanged): per layer the QKV
+    GEMM on [B * T, dim], the T-token ``rope_append``, ``attn_extend``, W_o and the MLP, with the rounding
+    points of ``decode_step``. Returns (h, pending) [B, T, dim] for :func:`_head`."""
+    B, T = tokens.shape
+    a = model.model_args
+    Hq, Hkv, D = a.n_heads, a.kv_heads, a.head_dim
+    nq = Hq * D
+    scale = 1.0 / math.sqrt(D)
+    emb = model.tok_embeddings.weight
+    h = F.embedding(tokens.contiguous(), emb, model._slot([emb]))
+    pending = None
+    for i, layer in enumerate(model.layers.values()):
+        if pending is None:
+            x, n1 = h, model._norm(layer.attention_norm, h, None)
+        else:
+            x, n1 = model._norm(layer.attention_norm, h, pending)
+        at = layer.attention
+        qkv = torch.mm(n1.reshape(B * T, n1.shape[-1]), model._weight(_qkv_params(at)).t())
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i])
+        o, _ = attention_extend(qkv[:, :nq].view(B, T, Hq, D), cache.k[i], cache.v[i], cache.kv_len, scale)
+        att = F._mm_nt(o.view(B * T, nq), model._weight([at.wo.weight]), "o").view(B, T, -1)
+        h, n2 = model._norm(layer.ffn_norm, x, att)
+        pending = _mlp(model, layer, n2)
+    return h, pending
+
+
 @torch.no_grad()
-def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache) -> torch.Tensor:
+def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, return_all: bool = False) -> torch.Tensor:
+    """Append ``n_new[b]`` tokens (``tokens`` [B, T] right-padded, 1 <= n_new[b] <= T, values outside are
+    clamped) to every sequence at its own ``kv_len[b]`` -> logits [B, V] of row n_new[b] - 1, the next
+    position's; ``kv_len += n_new`` (clamped at the capacity). A follow-up turn, a continuation after a
+    shared prefix, one piece of a chunked prefill, the pass a speculative verifier needs.
+
+    All T rows are computed: the pad rows' k / v land beyond the new ``kv_len`` and are overwritten by
+    whatever is appended next, as prompt padding is in :func:`prefill`. A token whose position is at or
+    beyond the capacity stores nothing and attends to the whole cache (T = 1 overwrites the last row, as
+    ``decode_step`` does). ``n_new`` and ``kv_len`` stay on the device: no host synchronisation.
+    ``return_all=True`` returns the logits of every row, [B, T, V], instead (scoring; pad rows included).
+    fp8 caches are refused with ``ValueError``."""
+    if tokens.dim() != 2 or tokens.shape[1] < 1:
+        raise ValueError(f"extend: tokens must be [B, T] with T >= 1, got {tuple(tokens.shape)}")
+    B, T = tokens.shape
+    _check_cache(model, cache, B)
+    _refuse_fp8(cache, "extend")
+    n_new = n_new.to(device=tokens.device, dtype=torch.long).clamp(1, T)
+    h, pending = _extend_layers(model, tokens, cache)
+    cache.kv_len.copy_((cache.kv_len + n_new).clamp(max=cache.capacity))
+    if return_all:
+        return _head(model, h, pending)
+    bi = torch.arange(B, device=tokens.device)
+    rows = n_new - 1
+    return _head(model, h[bi, rows].contiguous(), None if pending is None else pending[bi, rows].contiguous())
+
+
+def _prefill_chunked(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chunk: int) -> torch.Tensor:
+    """:func:`prefill` in pieces of ``chunk`` columns, each an append onto the cache so far at the uniform base
+    c0 (``kv_len`` is set to it before the piece). The rows lens[b] - 1 are picked out of the piece they
+    fall in with a select on the device; the head runs once, on those B rows."""
+    B, S = tokens.shape
+    rows = (lens - 1).clamp(0, S - 1)
+    bi = torch.arange(B, device=tokens.device)
+    h_sel = p_sel = None
+    for c0 in range(0, S, chunk):
+        piece = tokens[:, c0:c0 + chunk]
+        cache.kv_len.fill_(c0)
+        h, pending = _extend_layers(model, piece, cache)
+        local = (rows - c0).clamp(0, piece.shape[1] - 1)
+        here = ((rows >= c0) & (rows < c0 + piece.shape[1])).unsqueeze(-1)
+        hr = h[bi, local]
+        h_sel = hr if h_sel is None else torch.where(here, hr, h_sel)
+        if pending is not None:
+            pr = pending[bi, local]
+            p_sel = pr if p_sel is None else torch.where(here, pr, p_sel)
+    cache.kv_len.copy_(lens.clamp(0, cache.capacity))
+    return _head(model, h_sel.contiguous(), None if p_sel is None else p_sel.contiguous())
+
+
+@torch.no_grad()
+def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chunk: int = 0) -> torch.Tensor:
     """tokens [B, S] (ragged prompts right-padded), lens [B] in 1 .. S -> logits [B, V] of row
     lens[b] - 1 of each sequence. Fills the cache rows 0 .. S - 1 and sets kv_len = lens. Causal
     attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist.
@@ -212,12 +321,22 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache) -> 
     With an fp8 cache the attention over the prompt still runs on the unquantized k / v; only what is
     stored is quantized. The logits returned here, the first generated token's, are therefore bit-equal to
     those of the ``"model"`` cache, and ``prefill(p)`` + ``decode_step(t)`` and ``prefill(p + t)`` see
-    different keys for the prompt: dequantized ones in the first, the 16-bit ones in the second."""
+    different keys for the prompt: dequantized ones in the first, the 16-bit ones in the second.
+
+    ``chunk > 0`` feeds the prompt in pieces of ``chunk`` columns, each an append onto the cache so far
+    (the layer body of :func:`extend`): peak activation memory scales with B * chunk, not B * S, and the
+    result is the one-shot prefill's up to summation order. It refuses an fp8 cache (``ValueError``): a
+    piece would attend to dequantized keys. ``chunk = 0`` is the one-shot path."""
     B, S = tokens.shape
     _check_cache(model, cache, B)
     if S > cache.capacity:
         raise ValueError(f"prompt length {S} exceeds the cache capacity {cache.capacity}")
     lens = lens.to(device=tokens.device, dtype=torch.long)
+    if chunk < 0:
+        raise ValueError(f"prefill: chunk must be >= 0, got {chunk}")
+    if chunk > 0:
+        _refuse_fp8(cache, "prefill(chunk > 0)")
+        return _prefill_chunked(model, tokens, lens, cache, int(chunk))
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens, emb, model._slot([emb]))
     pending = None
@@ -426,7 +545,7 @@ def _graph_refusal(model, device, dtype, sampler: str, temperature: float, use_c
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
              stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
-             kv_cache_dtype: str = "model") -> Tuple[List[List[int]], List[str]]:
+             kv_cache_dtype: str = "model", prefill_chunk: int = 0) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -450,7 +569,12 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     head) (:class:`KVCache`): about half the cache memory and half the bytes a decode step reads. The
     prompt's attention runs unquantized (:func:`prefill`), so the first generated token is the one the
     ``"model"`` cache gives; later tokens attend to dequantized keys and values. It needs the cache:
-    ``use_cache=False`` raises ``ValueError``."""
+    ``use_cache=False`` raises ``ValueError``.
+
+    ``prefill_chunk=N`` (N > 0) feeds the prompt through :func:`prefill` in pieces of N columns, bounding the
+    prefill's activation memory by B * N rows; the tokens are those of the one-shot prefill up to summation
+    order. It needs the cache and refuses ``kv_cache_dtype="fp8"``. ``stats["prefill_chunks"]`` is the number
+    of pieces (0: the one-shot prefill)."""
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
     if sampler not in ("torch", "philox"):
@@ -459,6 +583,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         raise ValueError(f"generate: kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
     if kv_cache_dtype != "model" and not use_cache:
         raise ValueError(f"generate: kv_cache_dtype={kv_cache_dtype!r} needs the KV cache (use_cache=True)")
+    if prefill_chunk < 0 or (prefill_chunk > 0 and not use_cache):
+        raise ValueError("generate: prefill_chunk must be >= 0 and needs the KV cache (use_cache=True)")
     device, dtype = _model_device_dtype(model)
     if graph:
         why = _graph_refusal(model, device, dtype, sampler, temperature, use_cache)
@@ -490,7 +616,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     timer.mark()
     if use_cache:
         cache = KVCache(args, B, cap, dtype, device, kv_cache_dtype)
-        logits = prefill(model, buf[:, :S], lens, cache)
+        logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk)
     else:
         bi = torch.arange(B, device=device)
         logits = model(buf[:, :S])[bi, lens - 1]
@@ -549,6 +675,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         stats["prefill_ms"] = t[0]
         stats["decode_ms_per_token"] = t[1] / steps if steps else 0.0
         stats["decode_steps"] = steps
+        stats["prefill_chunks"] = -(-S // prefill_chunk) if prefill_chunk > 0 else 0
         stats["graph_replays"] = max(0, dgraph.steps - DecodeGraph.WARMUP) if graph else 0
 
     out_h, count_h = out.cpu(), count.cpu().tolist()

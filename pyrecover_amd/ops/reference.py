@@ -229,28 +229,66 @@ def attention_decode_ref(q, k_cache, v_cache, kv_len, scale: Optional[float] = N
     return o.reshape(B, Hq, D), lse.reshape(B, Hq)
 
 
+def attention_extend_ref(q, k_cache, v_cache, kv_len, scale: Optional[float] = None):
+    """T new queries per sequence over a KV cache that already holds their own k / v, in the input's
+    precision promoted to at least fp32 (HIP: csrc/kernels/attention_extend.hip).
+
+    q [B, T, Hq, D]; k_cache, v_cache [B, cap, Hkv, D]; kv_len integer [B], the tokens held BEFORE this
+    append (clamped into [0, cap]): query t of sequence b sits at position p = kv_len[b] + t and attends
+    to keys 0 .. min(p, cap - 1), so every row sees at least key 0. Whatever the caches hold beyond a
+    row's bound (NaN and Inf included) never reaches its output. Returns (o [B, T, Hq, D] in that
+    precision, lse [B, T, Hq])."""
+    B, T, Hq, D = q.shape
+    cap, Hkv = k_cache.shape[1], k_cache.shape[2]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    n = kv_len.to(device=q.device, dtype=torch.long).clamp(0, cap)
+    last = (n.view(B, 1) + torch.arange(T, device=q.device).view(1, T)).clamp(max=cap - 1)  # [B, T]
+    dead = torch.arange(cap, device=q.device).view(1, 1, cap) > last.unsqueeze(-1)  # [B, T, cap]
+    unseen = dead.all(dim=1)  # [B, cap]: keys no row of the sequence sees
+    qg = up(q).view(B, T, Hkv, Hq // Hkv, D)
+    kk = up(k_cache).masked_fill(unseen.view(B, cap, 1, 1), 0)
+    vv = up(v_cache).masked_fill(unseen.view(B, cap, 1, 1), 0)
+    s = torch.einsum("bthgd,bkhd->bthgk", qg, kk) * scale
+    s = s.masked_fill(dead.view(B, T, 1, 1, cap), float("-inf"))
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    o = torch.einsum("bthgk,bkhd->bthgd", p, vv)
+    return o.reshape(B, T, Hq, D), lse.reshape(B, T, Hq)
+
+
 def rope_append_ref(qkv, tab, kv_len, k_cache, v_cache) -> None:
-    """The new tokens' fused QKV rows [B, (Hq + 2 Hkv) D] at positions pos[b] = clamp(kv_len[b], 0, cap - 1):
-    q is rotated in place, the rotated k and the plain v are written into row pos[b] of the caches
-    (RoPE math of :func:`rope_inplace_2d`: opmath rotation from table row pos[b], one rounding)."""
-    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape[1:])
+    """The fused QKV rows [B * T, (Hq + 2 Hkv) D] of T new tokens per sequence (B is the caches'), row
+    b * T + t at position p = clamp(kv_len[b], 0, cap) + t: q is rotated in place, the rotated k and the
+    plain v are written into row p of the caches (RoPE math of :func:`rope_inplace_2d`: opmath rotation
+    from table row p, one rounding). T = 1 clamps the row into the cache, pos[b] = clamp(kv_len[b], 0,
+    cap - 1); with T > 1 a row with p >= cap stores nothing and its q takes table row cap - 1."""
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape)
     k_cache[bi, pos] = k
     v_cache[bi, pos] = v
 
 
-def _rope_new_rows(qkv, tab, kv_len, cap: int, Hkv: int, D: int):
-    """Rotates q in place; returns (batch index, pos, rotated k [B, Hkv, D] in qkv's dtype, v [B, Hkv, D])."""
-    B = qkv.shape[0]
+def _rope_new_rows(qkv, tab, kv_len, B: int, cap: int, Hkv: int, D: int):
+    """Rotates q in place; returns, for the rows that are stored, (batch index, pos, rotated k [n, Hkv, D] in
+    qkv's dtype, v [n, Hkv, D])."""
+    N = qkv.shape[0]
+    T = N // B
     nk = Hkv * D
     nq = qkv.shape[1] - 2 * nk
-    pos = kv_len.to(device=qkv.device, dtype=torch.long).clamp(0, cap - 1)
-    rows = tab[pos].to(up(qkv).dtype)  # [B, D/2, 2]
+    at = (kv_len.to(device=qkv.device, dtype=torch.long).clamp(0, cap).view(B, 1) +
+          torch.arange(T, device=qkv.device).view(1, T)).reshape(N)
+    pos = at.clamp(max=cap - 1)
+    rows = tab[pos].to(up(qkv).dtype)  # [N, D/2, 2]
     c, s = rows[..., 0].unsqueeze(1), rows[..., 1].unsqueeze(1)
-    x = up(qkv[:, :nq + nk]).reshape(B, (nq + nk) // D, D // 2, 2)
+    x = up(qkv[:, :nq + nk]).reshape(N, (nq + nk) // D, D // 2, 2)
     a, b = x[..., 0], x[..., 1]
-    rot = torch.stack([a * c - b * s, a * s + b * c], dim=-1).reshape(B, nq + nk).to(qkv.dtype)
+    rot = torch.stack([a * c - b * s, a * s + b * c], dim=-1).reshape(N, nq + nk).to(qkv.dtype)
     qkv[:, :nq] = rot[:, :nq]
-    return torch.arange(B, device=qkv.device), pos, rot[:, nq:].view(B, Hkv, D), qkv[:, nq + nk:].view(B, Hkv, D)
+    bi = torch.arange(B, device=qkv.device).repeat_interleave(T)
+    k, v = rot[:, nq:].view(N, Hkv, D), qkv[:, nq + nk:].view(N, Hkv, D)
+    if T == 1:
+        return bi, pos, k, v
+    keep = at < cap  # a data-dependent selection: the torch path may synchronise, the HIP kernel does not
+    return bi[keep], pos[keep], k[keep], v[keep]
 
 
 # ---------------------------------------------------------------------------------------
@@ -280,7 +318,7 @@ def rope_append_fp8_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale) ->
     """:func:`rope_append_ref` over an fp8 cache: q is rotated in place as there; the k row is rotated in
     opmath, rounded once to qkv's dtype and then quantized, the v row quantized from its values: the cache
     is a pure function of what the 16-bit cache would hold."""
-    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape[1:])
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape)
     k_cache[bi, pos], k_scale[bi, pos] = kv_quantize_ref(k)
     v_cache[bi, pos], v_scale[bi, pos] = kv_quantize_ref(v)
 

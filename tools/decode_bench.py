@@ -13,6 +13,14 @@ Every timed call reads another layer's cache (as a decode step does), and the la
     python tools/decode_bench.py --shapes 7b --sampler both --graph     # whole tokens: sample + bookkeeping + step
     python tools/decode_bench.py --sample-bench                         # the sampler alone
     python tools/decode_bench.py --kv-cache-dtype both                  # the fp8 cache beside the 16-bit one
+    python tools/decode_bench.py --extend 8 --shapes llama3-8b          # attn_extend alone: 8 tokens onto a full cache
+    python tools/decode_bench.py --extend 2048 --extend-base 0 --shapes 7b --batch 4 --ctx 2048   # ... beside docs_fwd
+    python tools/decode_bench.py --prefill 4096 --prefill-chunk 0,512 --shapes 7b --batch 4 --layers 32
+
+``--extend T`` times ``attn_extend`` (csrc/kernels/attention_extend.hip) alone: T new queries per sequence over
+a cache that held ``--extend-base`` keys before (default ctx - T). ``--prefill S`` times ``prefill`` of a B x S
+prompt once per ``--prefill-chunk`` value and prints the peak activation memory of each. ``--batch`` / ``--ctx``
+override the shapes' batch and context.
 
 ``--kv-cache-dtype model|fp8|both`` picks the cache of every table: ``fp8`` is the e4m3fn cache with one
 power-of-two scale per (token, kv head) (``attn_decode_fp8``; its K/V rate counts the bytes it reads, scales
@@ -106,6 +114,72 @@ def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
               f"KC={C.attn_decode_fp8_chunk()}): {hip / hip8:.2f}x of the 16-bit call; "
               f"max |o - o_ref(dequantized)| {err8:.2e}")
     return hip, tor
+
+
+def bench_extend(name, cfg, B, ctx, T, base, iters, dev):
+    """``attn_extend`` alone: T new queries per sequence over a cache of capacity ctx that held ``base`` keys
+    before the append (default ctx - T: the append fills the cache). With base 0 the call is a causal forward,
+    and the document-masked forward (one document per row) is timed at the same shape beside it."""
+    C = _ext.native()
+    Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
+    base = ctx - T if base is None else base
+    if T < 1 or base < 0 or base + T > ctx:
+        raise SystemExit(f"--extend: need 1 <= T and 0 <= base and base + T <= ctx, got T={T} base={base} ctx={ctx}")
+    per_layer = 2 * B * (base + T) * Hkv * D * 2  # bytes of K and V the keys of one call hold
+    n_buf = max(2, -(-2 * L3_BYTES // per_layer))
+    ks = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    vs = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    q = torch.randn(B, T, Hq, D, device=dev).bfloat16()
+    n = torch.full((B,), base, device=dev, dtype=torch.int32)
+    scale = 1 / math.sqrt(D)
+    flop = 4.0 * B * Hq * D * sum(base + t + 1 for t in range(T))  # q.k and p.v over the visible keys
+    hip = timed_us(lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale), iters)
+    o, _ = C.attn_extend(q, ks[0], vs[0], n, scale)
+    blocks = -(-T * (Hq // Hkv) // 128) * Hkv * B
+    print(f"{name}: attn_extend B={B} T={T} over kv_len={base} (cap {ctx}) Hq/Hkv={Hq}/{Hkv} D={D}: {blocks} blocks, "
+          f"{per_layer / 2**20:.0f} MiB of K/V, {n_buf} caches in rotation")
+    print(f"  HIP   {hip:9.1f} us  {flop / hip / 1e6:7.1f} TFLOP/s  {per_layer / hip / 1e6:6.2f} TB/s of K/V read once")
+    if T * B * ctx <= 1 << 24:  # the oracle materialises [B, T, Hq, ctx] scores
+        o_ref, _ = ref.attention_extend_ref(q.float(), ks[0].float(), vs[0].float(), n, scale)
+        print(f"  max |o - o_ref| {(o.float() - o_ref).abs().max().item():.2e}")
+    if base == 0 and T % 128 == 0:
+        ds = torch.zeros(B, T, dtype=torch.int32, device=dev)
+        kk, vv = [k[:, :T] for k in ks], [v[:, :T] for v in vs]
+        docs = timed_us(lambda i: C.attn_fwd(q, kk[i % n_buf], vv[i % n_buf], scale, True, ds), iters)
+        od, _ = C.attn_fwd(q, kk[0], vv[0], scale, True, ds)
+        print(f"  docs_fwd, one document per row, same shape: {docs:9.1f} us  {flop / docs / 1e6:7.1f} TFLOP/s "
+              f"(attn_extend takes {hip / docs:.2f}x; max |o - o_docs| {(o.float() - od.float()).abs().max().item():.2e})")
+    return hip
+
+
+def bench_prefill(name, preset, B, S, layers, chunks, iters, dev):
+    """``prefill`` of a B x S prompt, one-shot (chunk 0) and in pieces: milliseconds and the peak of
+    ``torch.cuda.max_memory_allocated`` above what the model and the cache hold."""
+    cfg = get_preset(preset, n_layers=layers, seq_len=S)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.bfloat16)
+    with torch.device(dev):
+        model = Transformer(cfg)
+    torch.set_default_dtype(prev)
+    model.eval()
+    model.flatten_(shadows=False)
+    cache = inf.KVCache(cfg, B, S, torch.bfloat16, dev)
+    tok = torch.randint(0, cfg.vocab_size, (B, S), device=dev)
+    lens = torch.full((B,), S, device=dev)
+    print(f"{name}: prefill of B={B} x S={S}, {layers} layers, bf16 (model + cache "
+          f"{torch.cuda.memory_allocated() / 2**30:.2f} GiB resident)")
+    first = None
+    for c in chunks:
+        inf.prefill(model, tok, lens, cache, chunk=c)  # library warm-up and GEMM tuning at this piece's shapes
+        torch.cuda.synchronize()
+        resident = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        us = timed_us(lambda _: inf.prefill(model, tok, lens, cache, chunk=c), iters, 1)
+        peak = torch.cuda.max_memory_allocated() - resident
+        logits = inf.prefill(model, tok, lens, cache, chunk=c).float()
+        first = logits if first is None else first
+        print(f"  chunk {c:5d}: prefill_ms {us / 1e3:9.2f}  peak activations {peak / 2**30:7.3f} GiB  "
+              f"max |logits - logits(chunk {chunks[0]})| {(logits - first).abs().max().item():.3e}")
 
 
 def filled_cache(cfg, B, ctx, dev, kv_dtype):
@@ -242,13 +316,31 @@ def main():
     ap.add_argument("--sample-bench", action="store_true", help="time the sampler alone")
     ap.add_argument("--kv-cache-dtype", choices=("model", "fp8", "both"), default="model",
                     help="the cache of every table: the model's dtype, fp8 (e4m3fn bytes + scales), or both arms")
+    ap.add_argument("--extend", type=int, default=0, metavar="T",
+                    help="time attn_extend alone: T new queries per sequence appended to each shape's cache")
+    ap.add_argument("--extend-base", type=int, default=None, metavar="N",
+                    help="keys the cache held before the append (default: ctx - T; 0 also times docs_fwd beside it)")
+    ap.add_argument("--prefill", type=int, default=0, metavar="S",
+                    help="time prefill of a B x S prompt, once per --prefill-chunk value, with its peak memory")
+    ap.add_argument("--prefill-chunk", default="0,512", help="comma list of chunk sizes for --prefill (0: one-shot)")
+    ap.add_argument("--batch", type=int, default=0, help="override the batch of every chosen shape")
+    ap.add_argument("--ctx", type=int, default=0, help="override the context (cache capacity) of every chosen shape")
     a = ap.parse_args()
-    shapes = [s for s in SHAPES if s[0] in a.shapes.split(",")]
+    shapes = [(s[0], s[1], a.batch or s[2], a.ctx or s[3]) for s in SHAPES if s[0] in a.shapes.split(",")]
     kinds = ("model", "fp8") if a.kv_cache_dtype == "both" else (a.kv_cache_dtype,)
     dev = torch.device("cuda", 0)
     _ext.native()
     if a.sample_bench:
         bench_sampler(a.iters, dev)
+        return
+    if a.extend:
+        for name, preset, B, ctx in shapes:
+            bench_extend(name, get_preset(preset), B, ctx, a.extend, a.extend_base, a.iters, dev)
+        return
+    if a.prefill:
+        for name, preset, B, _ in shapes:
+            bench_prefill(name, preset, B, a.prefill, a.layers, [int(c) for c in a.prefill_chunk.split(",")],
+                          max(3, a.iters // 10), dev)
         return
     if a.sampler or a.graph:
         samplers = ("torch", "philox") if a.sampler == "both" else (a.sampler,) if a.sampler else ()
