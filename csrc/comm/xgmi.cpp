@@ -7,12 +7,14 @@
 // Memory: gradient buffers that peers read are allocated here with hipMalloc (exportable with
 // hipIpcGetMemHandle) and handed to torch as a tensor that frees them on destruction.
 // Synchronisation across processes uses interprocess HIP events (hipEventInterprocess):
-// a peer's stream waits GPU-side on this rank's event; no kernel ever spins on a flag.
+// a peer's stream waits GPU-side on this rank's event; no kernel ever spins on a flag. Where the
+// device has no interprocess events the host orders the ranks instead (XgmiEngine, host order).
 #include <torch/extension.h>
 #include <c10/core/DeviceGuard.h>
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -67,6 +69,34 @@ uintptr_t ipc_event_create(int64_t device) {
   hipEvent_t e;
   hchk(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventInterprocess), "hipEventCreate(ipc)");
   return (uintptr_t)e;
+}
+
+// An event of this process alone (the engine's own stream-to-stream waits when the peers are
+// ordered through the host, XgmiEngine host_order).
+uintptr_t event_create(int64_t device) {
+  hchk(hipSetDevice((int)device), "hipSetDevice");
+  hipEvent_t e;
+  hchk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+  return (uintptr_t)e;
+}
+
+// Whether this device exports and records interprocess events. The runtime keeps an interprocess
+// event's signals in a shared page that it registers with the GPU (hipHostRegister); where host
+// memory cannot be registered -- a GPU passed through to a virtual machine -- hipIpcGetEventHandle
+// and hipEventRecord on such an event fail with "invalid argument". The failed calls' error is taken
+// off the runtime's last-error slot, so the next kernel launch check does not report it.
+bool ipc_events_supported(int64_t device) {
+  hchk(hipSetDevice((int)device), "hipSetDevice");
+  hipEvent_t e;
+  bool ok = hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventInterprocess) == hipSuccess;
+  if (ok) {
+    hipIpcEventHandle_t h;
+    ok = hipIpcGetEventHandle(&h, e) == hipSuccess && hipEventRecord(e, nullptr) == hipSuccess &&
+         hipEventSynchronize(e) == hipSuccess;
+    (void)hipEventDestroy(e);
+  }
+  (void)hipGetLastError();
+  return ok;
 }
 
 py::bytes ipc_event_handle(uintptr_t e) {
@@ -172,18 +202,26 @@ void sparse_rows(int phase, const std::vector<uintptr_t>& grads, const std::vect
 // pra_sparse_rows over the W mapped gradients and the W mapped sorted id lists, with the same
 // events ("ready": gradient and id list written; "reduced": owned union rows summed). Every rank ends
 // with every union row, in both modes, like the dense all-reduce of that bucket.
+// Host order (host_order; devices without interprocess events, ipc_events_supported): the same
+// schedule with the sequence words alone between the processes. A word is then written by a host
+// function on the stream (hipLaunchHostFunc), i.e. once the work it stands for has COMPLETED, not when
+// an event was recorded, and a rank enqueues what depends on a peer's word only after reading it, so
+// no stream waits on a peer's event (the peer_* lists are unused; ev_ready / ev_upd are events of this
+// process, for its own comm stream). The ordering arguments above hold with "the word was
+// written" in place of "the event completed"; the worker then waits for the peers' GPUs at every
+// phase instead of running ahead of them.
 class XgmiEngine {
  public:
   XgmiEngine(int device, int rank, int world, int dtype, int64_t esz, std::vector<uintptr_t> peer_base,
              std::vector<int64_t> cuts, uintptr_t seq_words, std::vector<uintptr_t> ev_ready,
              std::vector<uintptr_t> ev_rs, uintptr_t ev_step, std::vector<uintptr_t> peer_ready,
              std::vector<uintptr_t> peer_rs, std::vector<uintptr_t> peer_step, std::vector<uintptr_t> peer_pbase,
-             std::vector<uintptr_t> ev_upd, std::vector<uintptr_t> peer_upd)
+             std::vector<uintptr_t> ev_upd, std::vector<uintptr_t> peer_upd, bool host_order)
       : dev_(device), rank_(rank), world_(world), dtype_(dtype), esz_(esz), base_(std::move(peer_base)),
         cuts_(std::move(cuts)), words_(reinterpret_cast<int64_t*>(seq_words)), ev_ready_(std::move(ev_ready)),
         ev_rs_(std::move(ev_rs)), ev_step_(ev_step), peer_ready_(std::move(peer_ready)),
         peer_rs_(std::move(peer_rs)), peer_step_(std::move(peer_step)), pbase_(std::move(peer_pbase)),
-        ev_upd_(std::move(ev_upd)), peer_upd_(std::move(peer_upd)) {
+        ev_upd_(std::move(ev_upd)), peer_upd_(std::move(peer_upd)), host_order_(host_order) {
     nb_ = (int)ev_ready_.size();
     shard_ = !pbase_.empty();
     TORCH_CHECK(world_ >= 2 && world_ <= 16 && (int)base_.size() == world_, "XgmiEngine: 2..16 ranks");
@@ -215,6 +253,10 @@ class XgmiEngine {
     }
     cv_.notify_all();
     if (worker_.joinable()) worker_.join();
+    // no host function that writes a word may be left on a stream (bounded, like every wait here)
+    const auto t0 = std::chrono::steady_clock::now();
+    while (notes_.load(std::memory_order_acquire) > 0 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(60))
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
     for (auto e : done_) (void)hipEventDestroy(e);
     for (auto e : gdone_) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(comm_);
@@ -274,7 +316,7 @@ class XgmiEngine {
       std::lock_guard<std::mutex> g(mu_);
       seq = seq_;
     }
-    publish(2 * nb_ + b, seq);
+    post((hipStream_t)cur, 2 * nb_ + b, seq);
     push(nb_ + b);
     return seq;
   }
@@ -302,7 +344,8 @@ class XgmiEngine {
         err_ = "step barrier " + std::to_string(seq_) + " not reached in 600 s";
     }
     check_err();
-    for (int r = 0; r < world_; ++r)
+    // host order: the worker has read every peer's step word, written behind that peer's last kernel
+    for (int r = 0; r < world_ && !host_order_; ++r)
       if (r != rank_) hchk(hipStreamWaitEvent((hipStream_t)cur, (hipEvent_t)peer_step_[r], 0), "wait step");
     std::lock_guard<std::mutex> g(mu_);
     ++seq_;
@@ -323,6 +366,40 @@ class XgmiEngine {
   }
   int64_t& word(int r, int slot) { return words_[(int64_t)r * words_per_rank(nb_) + slot]; }
   void publish(int slot, int64_t v) { __atomic_store_n(&word(rank_, slot), v, __ATOMIC_RELEASE); }
+  struct Note {
+    XgmiEngine* eng;
+    int slot;
+    int64_t seq;
+  };
+  static void note_cb(void* p) {
+    Note* n = static_cast<Note*>(p);
+    n->eng->publish(n->slot, n->seq);
+    n->eng->notes_.fetch_sub(1, std::memory_order_release);
+    delete n;
+  }
+  // This rank's part of `slot` for step `seq` is enqueued on `st` (and, with interprocess events, the
+  // slot's event recorded behind it): the word says so at once; in host order it is written by a host
+  // function on `st`, once that work has completed.
+  void post(hipStream_t st, int slot, int64_t seq) {
+    if (!host_order_) return publish(slot, seq);
+    Note* n = new Note{this, slot, seq};
+    notes_.fetch_add(1, std::memory_order_relaxed);
+    const hipError_t e = hipLaunchHostFunc(st, note_cb, n);
+    if (e != hipSuccess) {
+      notes_.fetch_sub(1, std::memory_order_release);
+      delete n;
+    }
+    hchk(e, "hipLaunchHostFunc");
+  }
+  void mark(uintptr_t ev, hipStream_t st, int slot, int64_t seq, const char* what) {
+    if (!host_order_) hchk(hipEventRecord((hipEvent_t)ev, st), what);
+    post(st, slot, seq);
+  }
+  // Rank r's part of `slot` precedes what is enqueued on `st` from here on.
+  void await(int r, int slot, int64_t seq, hipStream_t st, uintptr_t ev, const char* what) {
+    wait_word(r, slot, seq);
+    if (!host_order_) hchk(hipStreamWaitEvent(st, (hipEvent_t)ev, 0), what);
+  }
   // bounded: a peer that never gets there is reported with the bucket and the phase it missed
   void wait_word(int r, int slot, int64_t v) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -348,13 +425,9 @@ class XgmiEngine {
       l[r] = (const int64_t*)sp_ids_[r];
     }
     hchk(pra_sparse_rows(dtype_, 1, g.data(), l.data(), world_, rank_, sp_n_, sp_V_, sp_D_, st), "sparse reduce");
-    hchk(hipEventRecord((hipEvent_t)ev_rs_[b], st), "record reduced");
-    publish(nb_ + b, seq);
-    for (int r = 0; r < world_; ++r) {
-      if (r == rank_) continue;
-      wait_word(r, nb_ + b, seq);
-      hchk(hipStreamWaitEvent(st, (hipEvent_t)peer_rs_[(int64_t)r * nb_ + b], 0), "wait peer reduced");
-    }
+    mark(ev_rs_[b], st, nb_ + b, seq, "record reduced");
+    for (int r = 0; r < world_; ++r)
+      if (r != rank_) await(r, nb_ + b, seq, st, peer_rs_[(int64_t)r * nb_ + b], "wait peer reduced");
     hchk(pra_sparse_rows(dtype_, 2, g.data(), l.data(), world_, rank_, sp_n_, sp_V_, sp_D_, st), "sparse gather");
     hchk(hipEventRecord(done_[b], st), "record done");
   }
@@ -368,8 +441,7 @@ class XgmiEngine {
     std::vector<long> gn;
     for (int r = 0; r < world_; ++r) {
       if (r == rank_) continue;
-      wait_word(r, 2 * nb_ + b, seq);
-      hchk(hipStreamWaitEvent(st, (hipEvent_t)peer_upd_[(int64_t)r * nb_ + b], 0), "wait peer updated");
+      await(r, 2 * nb_ + b, seq, st, peer_upd_[(int64_t)r * nb_ + b], "wait peer updated");
       const int64_t p0 = c[r], pn = c[r + 1] - p0;
       if (pn > 0) {
         gs.push_back((const void*)(pbase_[r] + p0 * esz_));
@@ -385,13 +457,10 @@ class XgmiEngine {
     const int64_t s0 = c[rank_], n = c[rank_ + 1] - s0;
     hipStream_t st = comm_;
     // reduce-scatter: every rank's bucket b is complete (GPU-side waits), then one pull-reduce
-    publish(b, seq);
     hchk(hipStreamWaitEvent(st, (hipEvent_t)ev_ready_[b], 0), "wait own ready");
-    for (int r = 0; r < world_; ++r) {
-      if (r == rank_) continue;
-      wait_word(r, b, seq);
-      hchk(hipStreamWaitEvent(st, (hipEvent_t)peer_ready_[(int64_t)r * nb_ + b], 0), "wait peer ready");
-    }
+    post(st, b, seq);
+    for (int r = 0; r < world_; ++r)
+      if (r != rank_) await(r, b, seq, st, peer_ready_[(int64_t)r * nb_ + b], "wait peer ready");
     if (b == sparse_b_) {
       sparse(b, seq);
       return;
@@ -403,16 +472,14 @@ class XgmiEngine {
       hchk(hipEventRecord(done_[b], st), "record done");
       return;
     }
-    hchk(hipEventRecord((hipEvent_t)ev_rs_[b], st), "record reduced");
-    publish(nb_ + b, seq);
+    mark(ev_rs_[b], st, nb_ + b, seq, "record reduced");
     // all-gather: every owner has reduced its slice, then one pull of all peers' slices
     std::vector<const void*> gs;
     std::vector<void*> gd;
     std::vector<long> gn;
     for (int r = 0; r < world_; ++r) {
       if (r == rank_) continue;
-      wait_word(r, nb_ + b, seq);
-      hchk(hipStreamWaitEvent(st, (hipEvent_t)peer_rs_[(int64_t)r * nb_ + b], 0), "wait peer reduced");
+      await(r, nb_ + b, seq, st, peer_rs_[(int64_t)r * nb_ + b], "wait peer reduced");
       const int64_t p0 = c[r], pn = c[r + 1] - p0;
       if (pn > 0) {
         gs.push_back((const void*)(base_[r] + p0 * esz_));
@@ -424,8 +491,7 @@ class XgmiEngine {
     hchk(hipEventRecord(done_[b], st), "record done");
   }
   void step(int64_t seq) {
-    hchk(hipEventRecord((hipEvent_t)ev_step_, comm_), "record step");
-    publish(3 * nb_, seq);
+    mark(ev_step_, comm_, 3 * nb_, seq, "record step");
     for (int r = 0; r < world_; ++r)
       if (r != rank_) wait_word(r, 3 * nb_, seq);
   }
@@ -470,6 +536,8 @@ class XgmiEngine {
   std::vector<uintptr_t> peer_ready_, peer_rs_, peer_step_;
   std::vector<uintptr_t> pbase_, ev_upd_, peer_upd_;  // sharded mode: parameter buffers, "updated" events
   bool shard_ = false;
+  const bool host_order_;         // no interprocess events: the sequence words alone order the ranks
+  std::atomic<int64_t> notes_{0};  // host functions enqueued and not yet run
   int sparse_b_ = -1;  // the bucket reduced as a sparse row exchange (set_sparse)
   int64_t sp_off_ = 0, sp_V_ = 0, sp_D_ = 0, sp_n_ = 0;
   std::vector<uintptr_t> sp_ids_;
@@ -496,6 +564,8 @@ void register_xgmi(py::module& m) {
   x.def("ipc_open_mem", &ipc_open_mem);
   x.def("ipc_close_mem", &ipc_close_mem);
   x.def("ipc_event_create", &ipc_event_create);
+  x.def("event_create", &event_create);
+  x.def("ipc_events_supported", &ipc_events_supported);
   x.def("ipc_event_handle", &ipc_event_handle);
   x.def("ipc_event_open", &ipc_event_open);
   x.def("event_destroy", &event_destroy);
@@ -510,12 +580,12 @@ void register_xgmi(py::module& m) {
       .def(py::init<int, int, int, int, int64_t, std::vector<uintptr_t>, std::vector<int64_t>, uintptr_t,
                     std::vector<uintptr_t>, std::vector<uintptr_t>, uintptr_t, std::vector<uintptr_t>,
                     std::vector<uintptr_t>, std::vector<uintptr_t>, std::vector<uintptr_t>, std::vector<uintptr_t>,
-                    std::vector<uintptr_t>>(),
+                    std::vector<uintptr_t>, bool>(),
            py::arg("device"), py::arg("rank"), py::arg("world"), py::arg("dtype"), py::arg("esz"),
            py::arg("peer_base"), py::arg("cuts"), py::arg("seq_words"), py::arg("ev_ready"), py::arg("ev_rs"),
            py::arg("ev_step"), py::arg("peer_ready"), py::arg("peer_rs"), py::arg("peer_step"),
            py::arg("peer_pbase") = std::vector<uintptr_t>(), py::arg("ev_upd") = std::vector<uintptr_t>(),
-           py::arg("peer_upd") = std::vector<uintptr_t>())
+           py::arg("peer_upd") = std::vector<uintptr_t>(), py::arg("host_order") = false)
       .def_static("words_per_rank", &XgmiEngine::words_per_rank)
       .def("set_sparse", &XgmiEngine::set_sparse)
       .def("gather", &XgmiEngine::gather)

@@ -1314,7 +1314,10 @@ class Reader {
               ssize_t got = -1;
               if (use_direct.load()) {
                 got = pread_full(fd, buf, (n + 4095) & ~uint64_t(4095), c);
-                if (got < 0 && errno == EINVAL) use_direct = false;
+                // EINVAL: the filesystem refuses the direct read. EFAULT: the kernel cannot pin the
+                // hipHostMalloc'ed staging buffer's pages for it (seen with a GPU passed through to a
+                // virtual machine); a buffered read copies into the same buffer all the same.
+                if (got < 0 && (errno == EINVAL || errno == EFAULT)) use_direct = false;
               }
               if (!use_direct.load()) {
                 if (bfd < 0) bfd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);

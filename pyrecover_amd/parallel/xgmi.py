@@ -21,7 +21,10 @@ Cross-process ordering uses interprocess HIP events only: a rank's comm stream w
 on its peers' "bucket ready" / "slice reduced" events, and no kernel spins. The host only
 guarantees that an event was recorded (for THIS step) before anyone waits on it: every rank
 publishes a per-bucket sequence number in a page of host shared memory right after recording, and
-the worker of a peer polls that word (microseconds). The backward thread never blocks.
+the worker of a peer polls that word (microseconds). The backward thread never blocks. On a device
+without interprocess events (a GPU passed through to a virtual machine) the engine runs in host
+order: a word is written by a host function on the stream once the work has completed, and the peers
+enqueue what depends on it after reading the word (``csrc/comm/xgmi.cpp``, host order).
 
 Sharded optimizer (``GradReducer(shard=True)``): the reduce-scatter is the pull-reduce alone, and
 after the AdamW update of the owned slice one pull-gather per bucket copies the peers' updated
@@ -243,14 +246,23 @@ class XgmiAllReduce:
         # 5) events: per bucket "ready" and "reduced" (and, sharded, "updated"; interprocess), one
         # per-step "done"
         nb = len(self.ranges)
-        self.ev_ready = [self.C.ipc_event_create(di) for _ in range(nb)]
-        self.ev_rs = [self.C.ipc_event_create(di) for _ in range(nb)]
-        self.ev_upd = [self.C.ipc_event_create(di) for _ in range(nb)] if self.shard else []
-        self.ev_step = self.C.ipc_event_create(di)
-        mine = ([self.C.ipc_event_handle(e) for e in self.ev_ready], [self.C.ipc_event_handle(e) for e in self.ev_rs],
-                self.C.ipc_event_handle(self.ev_step), [self.C.ipc_event_handle(e) for e in self.ev_upd])
+        # A device without interprocess events (a GPU passed through to a virtual machine: the runtime
+        # cannot register the events' shared page) on any rank: every rank runs the engine in host
+        # order, where the sequence words alone order the ranks and the events stay in their process
+        oks: List = [None] * W
+        dist.all_gather_object(oks, bool(self.C.ipc_events_supported(di)), group=self.hgroup)
+        self.host_order = not all(oks)
+        new_event = self.C.event_create if self.host_order else self.C.ipc_event_create
+        self.ev_ready = [new_event(di) for _ in range(nb)]
+        self.ev_rs = [new_event(di) for _ in range(nb)]
+        self.ev_upd = [new_event(di) for _ in range(nb)] if self.shard else []
+        self.ev_step = new_event(di)
         allh: List = [None] * W
-        dist.all_gather_object(allh, mine, group=self.hgroup)
+        if not self.host_order:
+            mine = ([self.C.ipc_event_handle(e) for e in self.ev_ready],
+                    [self.C.ipc_event_handle(e) for e in self.ev_rs],
+                    self.C.ipc_event_handle(self.ev_step), [self.C.ipc_event_handle(e) for e in self.ev_upd])
+            dist.all_gather_object(allh, mine, group=self.hgroup)
         self.peer_ready, self.peer_rs, self.peer_step, self.peer_upd = [], [], [], []
         for r in range(W):
             if r == self.rank:
@@ -258,6 +270,11 @@ class XgmiAllReduce:
                 self.peer_rs.append(self.ev_rs)
                 self.peer_step.append(self.ev_step)
                 self.peer_upd.append(self.ev_upd)
+            elif self.host_order:  # no stream ever waits on a peer's event
+                self.peer_ready.append([0] * nb)
+                self.peer_rs.append([0] * nb)
+                self.peer_step.append(0)
+                self.peer_upd.append([0] * len(self.ev_upd))
             else:
                 self.peer_ready.append([self.C.ipc_event_open(h, di) for h in allh[r][0]])
                 self.peer_rs.append([self.C.ipc_event_open(h, di) for h in allh[r][1]])
@@ -277,7 +294,7 @@ class XgmiAllReduce:
             list(self.ev_ready), list(self.ev_rs), self.ev_step,
             [e for r in range(W) for e in self.peer_ready[r]], [e for r in range(W) for e in self.peer_rs[r]],
             list(self.peer_step), list(self.peer_pbase), list(self.ev_upd),
-            [e for r in range(W) for e in self.peer_upd[r]] if self.shard else [])
+            [e for r in range(W) for e in self.peer_upd[r]] if self.shard else [], self.host_order)
         self.ids_buf = None  # sparse exchange: this rank's published id list (allocated at first use)
         dist.barrier(group=self.hgroup)
 

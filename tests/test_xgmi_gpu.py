@@ -37,6 +37,18 @@ def test_xgmi_allreduce_matches_process_group(cuda, tmp_path):
     assert torch.equal(a["params"], c["params"])
 
 
+def test_ipc_event_probe_leaves_no_error_behind(cuda):
+    """ipc_events_supported answers either way (a device without interprocess events runs the engine
+    in host order) and takes a failed call's error off the runtime: the next launch check is clean."""
+    from pyrecover_amd import _ext
+
+    ok = _ext.native().xgmi.ipc_events_supported(cuda.index or 0)
+    assert ok in (True, False)
+    x = torch.full((8,), 2.0, device=cuda)
+    assert (x * x).sum().item() == 32.0  # the launch check after the kernel raises on a pending error
+    torch.cuda.synchronize()
+
+
 def test_rccl_process_group_with_high_priority_stream(cuda):
     """The RCCL process-group options used by parallel/dist.py are accepted by this build."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
