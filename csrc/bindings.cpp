@@ -1000,10 +1000,13 @@ void rope_append_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_le
 // q [B, T, Hq, D] (token rows may be strided views of the QKV activation), caches [B, cap, Hkv, D] that hold
 // the T new tokens already, kv_len int32 [B] on the device (tokens held before this append)
 // -> (o [B, T, Hq, D], lse fp32 [B, T, Hq]). Query t attends to keys 0 .. min(kv_len[b] + t, cap - 1).
+// split: -1 by shape (attn_extend_plan), 0 single pass, 1 key split; the split's workspace is allocated here
+// only when the plan splits (at::empty: safe under hipGraph capture, as attn_decode's).
 std::vector<at::Tensor> attn_extend(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                                    const at::Tensor& kv_len, double scale) {
+                                    const at::Tensor& kv_len, double scale, int64_t split) {
   const Range range_("pyrecover::attn_extend");
   check_dev(q, "q");
+  TORCH_CHECK(split >= -1 && split <= 1, "attn_extend: split must be -1 (by shape), 0 or 1, got ", split);
   TORCH_CHECK(q.dim() == 4 && q.size(1) > 0, "attn_extend: q must be [B, T, Hq, D], got ", q.sizes());
   const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
   check_decode_common(q, k_cache, v_cache, kv_len, B, "attn_extend");
@@ -1021,11 +1024,32 @@ std::vector<at::Tensor> attn_extend(const at::Tensor& q, const at::Tensor& k_cac
   const c10::DeviceGuard guard(q.device());
   at::Tensor o = at::empty({B, T, Hq, D}, q.options());
   at::Tensor lse = at::empty({B, T, Hq}, q.options().dtype(at::kFloat));
+  pra_attn_extend_plan_t pl;
+  pra_attn_extend_plan((int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap, (int)split, &pl);
+  at::Tensor ws;
+  if (pl.split) ws = at::empty({pl.ws_floats}, q.options().dtype(at::kFloat));
   check(pra_attn_extend(dt(q), qc.data_ptr(), ldq, k_cache.data_ptr(), v_cache.data_ptr(),
-                        kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(), (int)B, (int)T, (int)Hq, (int)Hkv,
-                        (int)D, (int)cap, (float)scale, stream_of(q)),
+                        kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(),
+                        pl.split ? ws.data_ptr<float>() : nullptr, (int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap,
+                        (float)scale, (int)split, stream_of(q)),
         "attn_extend");
   return {o, lse};
+}
+
+// what attn_extend(split=-1) runs for this shape on the current device (csrc/kernels/attn_extend_plan.h)
+py::dict attn_extend_plan(int64_t B, int64_t T, int64_t Hq, int64_t Hkv, int64_t D, int64_t cap) {
+  TORCH_CHECK(B > 0 && T > 0 && Hkv > 0 && Hq > 0 && Hq % Hkv == 0 && (D == 64 || D == 128) && cap > 0 &&
+                  std::max({B, T, Hq, cap}) <= (int64_t)INT32_MAX / 2,
+              "attn_extend_plan: bad shape");
+  pra_attn_extend_plan_t pl;
+  pra_attn_extend_plan((int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap, -1, &pl);
+  py::dict d;
+  d["split"] = pl.split != 0;
+  d["ws_waves"] = pl.ws_waves;
+  d["chunks"] = pl.chunks;
+  d["blocks"] = pl.blocks;
+  d["ws_floats"] = pl.ws_floats;
+  return d;
 }
 
 // q [B, Hq, D] (rows may be strided views of the QKV activation), caches [B, cap, Hkv, D], kv_len int32 [B]
@@ -1381,7 +1405,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("scale"));
   m.def("attn_decode_chunk", []() { return pra_attn_decode_chunk(); });
   m.def("attn_extend", &attn_extend, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("kv_len"),
-        py::arg("scale"));
+        py::arg("scale"), py::arg("split") = -1);
+  m.def("attn_extend_plan", &attn_extend_plan, py::arg("B"), py::arg("T"), py::arg("Hq"), py::arg("Hkv"), py::arg("D"),
+        py::arg("cap"));
+  m.def("attn_extend_chunk", []() { return pra_attn_extend_chunk(); });
   m.def("kv_quantize_", &kv_quantize_, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("k_scale"), py::arg("v_scale"));
   m.def("rope_append_fp8_", &rope_append_fp8_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_cache"),

@@ -1236,15 +1236,6 @@ namespace {
 
 pra_attn_options g_attn_opts;  // attn_plan.h
 
-static int device_cus() {
-  static int cus[64] = {0};
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
-  if (cus[d] == 0 && (hipDeviceGetAttribute(&cus[d], hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || cus[d] <= 0))
-    cus[d] = 256;
-  return cus[d];
-}
-
 // bf16 / fp16 family: S a multiple of `tile` (64 forward, 128 backward), head_dim 64 or 128
 bool shape_ok(const pra_attn_args& a, int tile, bool bwd) {
   if (a.S % tile || (a.D != 64 && a.D != 128) || a.Hq % a.Hkv) return false;

@@ -19,8 +19,18 @@
 //    tiles that cross a row's bound. The staging load's row bound is bend + 1, so no key at or beyond
 //    min(kv_len[b] + nt, cap) is ever loaded (zeros stand in, and they are masked): whatever the cache
 //    holds there, NaN and Inf included, cannot reach an output.
-// One block walks all keys of its rows (no key split), no atomics, one fixed summation order: the same
-// bits from run to run, and a sequence's output does not depend on cap or on the rest of the batch.
+// In this kernel one block walks all keys of its rows: no atomics, one fixed summation order.
+//
+// Key split (attention_extend_split.hip). A short append over a long cache leaves this kernel with a handful
+// of blocks, each walking every key tile on one wave. pra_attn_extend then runs extend_split_kernel (keys cut
+// into fixed chunks of pra_attn_extend_chunk() keys, the waves of a block sharing a row tile and dividing the
+// chunk's key tiles) and extend_combine_kernel (the chunks' fp32 partials merged in ascending order). The
+// choice is extend_plan's (attn_extend_plan.h): `split` 0 / 1 forces it, -1 takes it from
+// (B, T, Hq, Hkv, D, cap, CU count) alone, never from device data.
+//
+// Contract, for a fixed split setting: a sequence's o / lse are a pure function of its own q, K, V,
+// kv_len[b] and T -- not of cap, the batch or the other lengths -- and come out with the same bits from run
+// to run. The two settings differ only in the order of the fp32 sums.
 // Compiled with -fno-honor-nans like attention_docs.hip: no NaN is formed.
 #include "attn_common.h"
 #include "common.h"
@@ -175,20 +185,34 @@ __global__ __launch_bounds__(256, 2) void extend_fwd_kernel(const T* __restrict_
 }  // namespace attn
 }  // namespace pra
 
-extern "C" hipError_t pra_attn_extend(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
-                                      const int* kv_len, void* o, float* lse, int B, int T, int Hq, int Hkv, int D,
-                                      int cap, float scale, hipStream_t s) {
+extern "C" {
+
+int pra_attn_extend_chunk() { return pra::attn::kExtendChunk; }
+
+long pra_attn_extend_ws_floats(int B, int T, int Hq, int D, int cap) {
+  return pra::attn::extend_ws_floats(B, T, Hq, D, cap);
+}
+
+void pra_attn_extend_plan(int B, int T, int Hq, int Hkv, int D, int cap, int split, pra_attn_extend_plan_t* out) {
+  *out = pra::attn::extend_plan(B, T, Hq, Hkv, D, cap, pra::attn::device_cus(), split);
+}
+
+hipError_t pra_attn_extend(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
+                           const int* kv_len, void* o, float* lse, float* ws, int B, int T, int Hq, int Hkv, int D,
+                           int cap, float scale, int split, hipStream_t s) {
   using namespace pra::attn;
   if (q == nullptr || k_cache == nullptr || v_cache == nullptr || kv_len == nullptr || o == nullptr || lse == nullptr)
     return hipErrorInvalidValue;
   if (B <= 0 || T <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv || (D != 64 && D != 128) || ldq % 8 ||
-      ldq < (long)Hq * D || (long)T * (Hq / Hkv) > 0x7fffffffL - 128 || (long)cap > 0x7fffffffL / 2)
+      ldq < (long)Hq * D || (long)T * (Hq / Hkv) > 0x7fffffffL - 128 || (long)cap > 0x7fffffffL / 2 || split < -1 ||
+      split > 1)
     return hipErrorInvalidValue;
-  const int R = T * (Hq / Hkv);
-  const long blocks = (long)((R + 127) / 128) * Hkv * B;
-  if (blocks > 0x7fffffffL) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)blocks), block(256);
   const float sl2 = scale * kLog2e;
+  const pra_attn_extend_plan_t pl = extend_plan(B, T, Hq, Hkv, D, cap, device_cus(), split);
+  if (pl.split)
+    return extend_split(dtype, q, ldq, k_cache, v_cache, kv_len, o, lse, ws, B, T, Hq, Hkv, D, cap, pl, sl2, s);
+  if (pl.blocks > 0x7fffffffL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)pl.blocks), block(256);
   return dispatch_16bit(dtype, [&](auto t) {
     using E = decltype(t);
     pra::dispatch(
@@ -199,4 +223,5 @@ extern "C" hipError_t pra_attn_extend(int dtype, const void* q, long ldq, const 
         HeadDim{D});
     return hipGetLastError();
   });
+}
 }

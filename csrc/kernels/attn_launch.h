@@ -13,6 +13,20 @@ hipError_t docs_bwd(const pra_attn_args& a, const BwdPlan& pl, hipStream_t st);
 hipError_t f32_fwd(const pra_attn_args& a, hipStream_t st);                      // attention_f32.hip
 hipError_t f32_bwd(const pra_attn_args& a, hipStream_t st);
 hipError_t fused_bwd(const pra_attn_args& a, const BwdPlan& pl, hipStream_t st);  // attention_bwd_fused.hip
+// attention_extend_split.hip: the key-split arm of pra_attn_extend (which has checked the shape)
+hipError_t extend_split(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
+                        const int* kv_len, void* o, float* lse, float* ws, int B, int T, int Hq, int Hkv, int D,
+                        int cap, const pra_attn_extend_plan_t& pl, float scale_log2, hipStream_t s);
+
+// CUs of the current device (256 when it cannot be asked): what the plans take as `cus`
+inline int device_cus() {
+  static int cus[64] = {0};
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return 256;
+  if (cus[d] == 0 && (hipDeviceGetAttribute(&cus[d], hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || cus[d] <= 0))
+    cus[d] = 256;
+  return cus[d];
+}
 
 inline Shape shape_of(const pra_attn_args& a) {
   const Family fam = a.doc_start != nullptr ? kFamDocs : a.dtype == kF32 ? kFamF32 : kFam16;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "attn_extend_plan.h"
 #include "attn_plan.h"
 #include "gemm_plan.h"
 
@@ -197,9 +198,15 @@ hipError_t pra_attn_decode_combine(int dtype, const float* ws_o, const float* ws
 // b * T + t of a [B * T][ldq] view (Hq * D columns, ldq % 8 == 0); query t of sequence b attends to keys
 // 0 .. min(clamp(kv_len[b], 0, cap) + t, cap - 1) of the caches, which hold the new tokens' k / v already
 // (pra_rope_append with nt = T runs first). o [B][T][Hq][D] contiguous, lse fp32 [B][T][Hq].
+// split: -1 by shape, 0 single pass, 1 key split (attention_extend_split.hip). pra_attn_extend_plan tells what
+// runs (attn_extend_plan.h); when it splits, ws holds its ws_floats = pra_attn_extend_ws_floats fp32 words
+// (16-B aligned), else ws is not read. pra_attn_extend_chunk: keys per chunk of the split.
 hipError_t pra_attn_extend(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
-                           const int* kv_len, void* o, float* lse, int B, int T, int Hq, int Hkv, int D, int cap,
-                           float scale, hipStream_t s);
+                           const int* kv_len, void* o, float* lse, float* ws, int B, int T, int Hq, int Hkv, int D,
+                           int cap, float scale, int split, hipStream_t s);
+void pra_attn_extend_plan(int B, int T, int Hq, int Hkv, int D, int cap, int split, pra_attn_extend_plan_t* out);
+long pra_attn_extend_ws_floats(int B, int T, int Hq, int D, int cap);
+int pra_attn_extend_chunk();
 
 // fp8 KV cache (attention_decode_fp8.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D] of
 // e4m3fn bytes, k_scale, v_scale fp32 [B][cap][Hkv], powers of two. dtype is the 16-bit type of qkv / q / o.

@@ -61,7 +61,9 @@ def _run(cmd):
 EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
                "attention_bwd_fused.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
                "attention_docs.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
-               "attention_extend.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"]}
+               "attention_extend.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
+               "attention_extend_split.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
+                                              "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def build(jobs: int = 8, force: bool = False, verbose: bool = False) -> str:

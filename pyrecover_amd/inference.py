@@ -12,6 +12,8 @@ argument depends on a host copy of it: a decode step never synchronises.
 ``extend`` appends T > 1 tokens per sequence to a cache that already holds keys (a follow-up turn, a
 continuation after a shared prefix, a scoring or verification pass): the T-token ``rope_append`` and
 ``attn_extend`` of csrc/kernels/attention_extend.hip (T queries per sequence over keys 0 .. kv_len[b] + t).
+A short append over a long cache runs its key-split arm (attention_extend_split.hip: fixed key chunks, fp32
+partials, an ordered combine) by a plan that reads shapes and the CU count only; see :func:`attention_extend`.
 ``prefill(chunk=N)`` feeds a prompt through it in pieces of N columns, so the prefill's activation memory
 is bounded by the piece. fp8 caches are refused by both.
 
@@ -138,14 +140,24 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     return o.to(q.dtype), lse
 
 
-def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
+                     split: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, T, Hq, D] over the caches [B, cap, Hkv, D], which hold the T new tokens' k / v already
     (:func:`rope_append` first); ``kv_len`` [B] counts the tokens held before the append. Query t of
     sequence b attends to keys 0 .. min(kv_len[b] + t, cap - 1). Returns (o [B, T, Hq, D] in q's dtype,
-    lse fp32 [B, T, Hq] -- the opmath dtype on the torch path)."""
+    lse fp32 [B, T, Hq] -- the opmath dtype on the torch path).
+
+    ``split`` picks the HIP kernel: ``False`` the single pass (one block walks all keys of its rows), ``True``
+    the key split of csrc/kernels/attention_extend_split.hip (fixed key chunks, fp32 partials, an ordered
+    combine), ``None`` by plan: ``attn_extend_plan`` chooses from (B, T, Hq, Hkv, D, cap, CU count) alone, never
+    from device data -- the split for a short append over a long cache, where the single pass leaves most CUs
+    idle. For a fixed setting a sequence's result is a pure function of its own q, K, V, ``kv_len[b]`` and T
+    (not of cap, the batch or the other lengths) with the same bits run to run; the two settings differ only
+    in fp32 summation order. The torch-math path ignores it."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if _decode_hip(q, q.shape[-1]):
-        o, lse = _ext.require_for(q).attn_extend(q, k_cache, v_cache, kv_len, scale)
+        o, lse = _ext.require_for(q).attn_extend(q, k_cache, v_cache, kv_len, scale,
+                                                 -1 if split is None else int(bool(split)))
         return o, lse
     o, lse = ref.attention_extend_ref(q, k_cache, v_cache, kv_len, scale)
     return o.to(q.dtype), lse

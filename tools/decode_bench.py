@@ -14,6 +14,7 @@ Every timed call reads another layer's cache (as a decode step does), and the la
     python tools/decode_bench.py --sample-bench                         # the sampler alone
     python tools/decode_bench.py --kv-cache-dtype both                  # the fp8 cache beside the 16-bit one
     python tools/decode_bench.py --extend 8 --shapes llama3-8b          # attn_extend alone: 8 tokens onto a full cache
+    python tools/decode_bench.py --extend 8 --extend-split 0 --shapes llama3-8b   # ... on the single pass (1: the key split)
     python tools/decode_bench.py --extend 2048 --extend-base 0 --shapes 7b --batch 4 --ctx 2048   # ... beside docs_fwd
     python tools/decode_bench.py --prefill 4096 --prefill-chunk 0,512 --shapes 7b --batch 4 --layers 32
 
@@ -116,10 +117,11 @@ def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
     return hip, tor
 
 
-def bench_extend(name, cfg, B, ctx, T, base, iters, dev):
+def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1):
     """``attn_extend`` alone: T new queries per sequence over a cache of capacity ctx that held ``base`` keys
     before the append (default ctx - T: the append fills the cache). With base 0 the call is a causal forward,
-    and the document-masked forward (one document per row) is timed at the same shape beside it."""
+    and the document-masked forward (one document per row) is timed at the same shape beside it. ``split``:
+    -1 by plan, 0 the single pass, 1 the key split."""
     C = _ext.native()
     Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
     base = ctx - T if base is None else base
@@ -133,10 +135,15 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev):
     n = torch.full((B,), base, device=dev, dtype=torch.int32)
     scale = 1 / math.sqrt(D)
     flop = 4.0 * B * Hq * D * sum(base + t + 1 for t in range(T))  # q.k and p.v over the visible keys
-    hip = timed_us(lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale), iters)
-    o, _ = C.attn_extend(q, ks[0], vs[0], n, scale)
-    blocks = -(-T * (Hq // Hkv) // 128) * Hkv * B
-    print(f"{name}: attn_extend B={B} T={T} over kv_len={base} (cap {ctx}) Hq/Hkv={Hq}/{Hkv} D={D}: {blocks} blocks, "
+    hip = timed_us(lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale, split), iters)
+    o, _ = C.attn_extend(q, ks[0], vs[0], n, scale, split)
+    on = C.attn_extend_plan(B, T, Hq, Hkv, D, ctx)["split"] if split < 0 else bool(split)
+    R, XC = T * (Hq // Hkv), C.attn_extend_chunk()
+    waves = (4 if R <= 32 else 2 if R <= 64 else 1) if on else 1  # waves that share a 32-row sub-tile
+    blocks = -(-R * waves // 128) * Hkv * B * (-(-ctx // XC) if on else 1)
+    arm = f"key split, XC={XC}, {waves} waves per sub-tile" if on else "single pass"
+    print(f"{name}: attn_extend B={B} T={T} over kv_len={base} (cap {ctx}) Hq/Hkv={Hq}/{Hkv} D={D}: "
+          f"{'plan: ' if split < 0 else ''}{arm}, {blocks} blocks, "
           f"{per_layer / 2**20:.0f} MiB of K/V, {n_buf} caches in rotation")
     print(f"  HIP   {hip:9.1f} us  {flop / hip / 1e6:7.1f} TFLOP/s  {per_layer / hip / 1e6:6.2f} TB/s of K/V read once")
     if T * B * ctx <= 1 << 24:  # the oracle materialises [B, T, Hq, ctx] scores
@@ -320,6 +327,8 @@ def main():
                     help="time attn_extend alone: T new queries per sequence appended to each shape's cache")
     ap.add_argument("--extend-base", type=int, default=None, metavar="N",
                     help="keys the cache held before the append (default: ctx - T; 0 also times docs_fwd beside it)")
+    ap.add_argument("--extend-split", choices=("auto", "0", "1"), default="auto",
+                    help="--extend: the kernel by plan (auto), the single pass (0) or the key split (1)")
     ap.add_argument("--prefill", type=int, default=0, metavar="S",
                     help="time prefill of a B x S prompt, once per --prefill-chunk value, with its peak memory")
     ap.add_argument("--prefill-chunk", default="0,512", help="comma list of chunk sizes for --prefill (0: one-shot)")
@@ -335,7 +344,8 @@ def main():
         return
     if a.extend:
         for name, preset, B, ctx in shapes:
-            bench_extend(name, get_preset(preset), B, ctx, a.extend, a.extend_base, a.iters, dev)
+            bench_extend(name, get_preset(preset), B, ctx, a.extend, a.extend_base, a.iters, dev,
+                         -1 if a.extend_split == "auto" else int(a.extend_split))
         return
     if a.prefill:
         for name, preset, B, _ in shapes:
