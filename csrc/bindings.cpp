@@ -1139,17 +1139,21 @@ void kv_quantize_(const at::Tensor& k, const at::Tensor& v, at::Tensor k_cache, 
 }
 
 // rope_append_ over an fp8 cache: q rotated in place (bit-equal), the rotated k row rounded to qkv's dtype and
-// the plain v row quantized into cache row clamp(kv_len[b], 0, cap - 1).
+// the plain v row quantized into the cache row of rope_append_: qkv [B * T, (Hq + 2 Hkv) D], row b * T + t at
+// position kv_len[b] + t; T = 1 clamps the row to cap - 1, T > 1 stores nothing for a position >= cap.
 void rope_append_fp8_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_len, at::Tensor k_cache,
                       at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale) {
   const Range range_("pyrecover::rope_append_fp8");
   check_dev(qkv, "qkv");
   check_row_major(qkv, "rope_append_fp8 qkv");
-  const int64_t B = qkv.size(0);
+  const int64_t B = k_cache.dim() == 4 ? k_cache.size(0) : qkv.size(0);
   check_decode_fp8_common(qkv, k_cache, v_cache, k_scale, v_scale, &kv_len, B, "rope_append_fp8");
   const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2), D = k_cache.size(3);
   TORCH_CHECK(qkv.size(1) % D == 0 && qkv.size(1) / D > 2 * Hkv && (qkv.size(1) / D - 2 * Hkv) % Hkv == 0,
               "rope_append_fp8: qkv must be [B, (Hq + 2 Hkv) D] with Hq a multiple of Hkv, got ", qkv.sizes());
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) % B == 0 && qkv.size(0) / B <= (int64_t)INT32_MAX / 2,
+              "rope_append_fp8: qkv must hold T rows for each of the caches' B = ", B, " sequences, got ", qkv.sizes());
+  const int64_t T = qkv.size(0) / B;
   TORCH_CHECK(qkv.stride(0) % 8 == 0, "rope_append_fp8: the qkv row stride must be a multiple of 8 elements");
   const int64_t Hq = qkv.size(1) / D - 2 * Hkv;
   same_dev(qkv, tab, "rope table");
@@ -1158,9 +1162,47 @@ void rope_append_fp8_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& k
               "rope_append_fp8: table must be contiguous fp32 [>= cap, D/2, 2]");
   const c10::DeviceGuard guard(qkv.device());
   check(pra_rope_append_fp8(dt(qkv), qkv.data_ptr(), tab.data_ptr(), kv_len.data_ptr<int>(), k_cache.data_ptr(),
-                            v_cache.data_ptr(), k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)B,
+                            v_cache.data_ptr(), k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), (int)B, (int)T,
                             qkv.stride(0), (int)Hq, (int)Hkv, (int)D, (int)cap, stream_of(qkv)),
         "rope_append_fp8");
+}
+
+// attn_extend over an fp8 cache (csrc/kernels/attention_extend_fp8.hip): the caches hold the T new tokens'
+// quantized rows already, and query t attends to the dequantized rows 0 .. min(kv_len[b] + t, cap - 1).
+// -> (o [B, T, Hq, D] in q's dtype, lse fp32 [B, T, Hq]). split and the workspace as attn_extend.
+std::vector<at::Tensor> attn_extend_fp8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& kv_len,
+                                        double scale, int64_t split) {
+  const Range range_("pyrecover::attn_extend_fp8");
+  check_dev(q, "q");
+  TORCH_CHECK(split >= -1 && split <= 1, "attn_extend_fp8: split must be -1 (by shape), 0 or 1, got ", split);
+  TORCH_CHECK(q.dim() == 4 && q.size(1) > 0, "attn_extend_fp8: q must be [B, T, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  check_decode_fp8_common(q, k_cache, v_cache, k_scale, v_scale, &kv_len, B, "attn_extend_fp8");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "attn_extend_fp8: q and the caches disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_extend_fp8: n_heads must be a multiple of n_kv_heads");
+  TORCH_CHECK(T * (Hq / Hkv) <= (int64_t)INT32_MAX / 2, "attn_extend_fp8: bad shape");
+  // rows of one token contiguous, tokens at one stride across the batch: else a packed copy
+  int64_t ldq = T > 1 ? q.stride(1) : B > 1 ? q.stride(0) : Hq * D;
+  const bool view_ok = q.stride(3) == 1 && q.stride(2) == D && ldq % 8 == 0 && ldq >= Hq * D &&
+                       (B == 1 || q.stride(0) == T * ldq);
+  at::Tensor qc = view_ok ? q : q.contiguous();
+  if (!view_ok) ldq = Hq * D;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_extend_fp8: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, T, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, T, Hq}, q.options().dtype(at::kFloat));
+  pra_attn_extend_plan_t pl;
+  pra_attn_extend_plan((int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap, (int)split, &pl);
+  at::Tensor ws;
+  if (pl.split) ws = at::empty({pl.ws_floats}, q.options().dtype(at::kFloat));
+  check(pra_attn_extend_fp8(dt(q), qc.data_ptr(), ldq, k_cache.data_ptr(), v_cache.data_ptr(),
+                            k_scale.data_ptr<float>(), v_scale.data_ptr<float>(), kv_len.data_ptr<int>(), o.data_ptr(),
+                            lse.data_ptr<float>(), pl.split ? ws.data_ptr<float>() : nullptr, (int)B, (int)T, (int)Hq,
+                            (int)Hkv, (int)D, (int)cap, (float)scale, (int)split, stream_of(q)),
+        "attn_extend_fp8");
+  return {o, lse};
 }
 
 // attn_decode over an fp8 cache -> (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq]).
@@ -1416,6 +1458,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode_fp8", &attn_decode_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"));
   m.def("attn_decode_fp8_chunk", []() { return pra_attn_decode_fp8_chunk(); });
+  m.def("attn_extend_fp8", &attn_extend_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"), py::arg("split") = -1);
   m.def("sample_", &sample_, py::arg("logits"), py::arg("tok"), py::arg("temperature"), py::arg("top_k"),
         py::arg("top_p"), py::arg("seed"), py::arg("pos") = py::none(), py::arg("ws") = py::none(),
         py::arg("u_out") = py::none(), py::arg("done") = py::none(), py::arg("count") = py::none(),

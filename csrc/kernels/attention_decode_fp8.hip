@@ -14,10 +14,10 @@
 //
 //   kv_quantize      prefill: the k and v views [B][S][Hkv][D] of the fused QKV activation into cache
 //                    rows 0 .. S - 1
-//   rope_append_fp8  rope_append_kernel with a quantizing store: q rotated in place (bit-equal), the k
-//                    row rotated in fp32, rounded once to the model dtype and then quantized, the v row
-//                    quantized from its 16-bit values: the cache is a pure function of what the 16-bit
-//                    cache would hold
+//   rope_append_fp8  rope_append_kernel (T tokens per sequence, its rows and overflow rule) with a
+//                    quantizing store: q rotated in place (bit-equal), the k row rotated in fp32, rounded
+//                    once to the model dtype and then quantized, the v row quantized from its 16-bit
+//                    values: the cache is a pure function of what the 16-bit cache would hold
 //   attn_decode_fp8  attn_decode_chunk_kernel over bytes: a 16-B load covers 16 columns, so D / 16
 //                    lanes cover a row. K bytes become 16-bit pairs (exact) for the packed dot with fp32
 //                    accumulate; the row's K scale multiplies the fp32 score, the V scale the
@@ -130,35 +130,40 @@ __device__ __forceinline__ void q8_rot_pair(float a, float b, float c, float s, 
   o1 = __builtin_fmaf(a, s, b * c);
 }
 
-// qkv [B][ld]: q (Hq heads) | k (Hkv) | v (Hkv), D columns each. One lane per 8 columns.
+// qkv [B * nt][ld]: q (Hq heads) | k (Hkv) | v (Hkv), D columns each, row b * nt + t at position
+// clamp(kv_len[b], 0, cap) + t. One lane per 8 columns. nt == 1 clamps the row to cap - 1; with nt > 1 a
+// position at or beyond cap stores nothing (its q takes table row cap - 1) but still takes part in the shuffles.
 template <typename T>
 __global__ __launch_bounds__(256) void rope_append_fp8_kernel(T* __restrict__ qkv, const float2* __restrict__ tab,
                                                               const int* __restrict__ kv_len, uint8_t* __restrict__ kq,
                                                               uint8_t* __restrict__ vq, float* __restrict__ ks,
-                                                              float* __restrict__ vs, int B, long ld, int Hq, int Hkv,
-                                                              int D, int cap) {
+                                                              float* __restrict__ vs, int B, int nt, long ld, int Hq,
+                                                              int Hkv, int D, int cap) {
   const int nq = Hq * D, nk = Hkv * D;
   const int lph = D / 8;
   const int vpr = (nq + 2 * nk) / 8;  // a multiple of lph
-  const long total = (long)B * vpr;
+  const long total = (long)B * nt * vpr;
   const int lane = threadIdx.x & 63;
   for (long base = (long)blockIdx.x * 256 + (threadIdx.x - lane); base < total; base += (long)gridDim.x * 256) {
     const long idx = base + lane;
     const bool live = idx < total;
     float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // what this lane quantizes (k, v lanes)
-    int kind = 0;                                            // 1: k row, 2: v row
+    int kind = 0;                                            // 1: k row, 2: v row (0 also for a row that is not stored)
     long row = 0;
     int cin = 0;  // column inside the k (or v) part
     if (live) {
-      const int b = (int)(idx / vpr);
-      const int col = (int)(idx - (long)b * vpr) * 8;
-      const int pos = min(max(kv_len[b], 0), cap - 1);
-      T* p = qkv + (long)b * ld + col;
+      const long r = idx / vpr;  // row b * nt + t
+      const int b = (int)(r / nt);
+      const int col = (int)(idx - r * vpr) * 8;
+      const int at = min(max(kv_len[b], 0), cap) + (int)(r - (long)b * nt);  // <= cap + nt - 1
+      const int pos = min(at, cap - 1);
+      const bool keep = at < cap || nt == 1;  // one token: the clamped row is overwritten
+      T* p = qkv + r * ld + col;
       float v[8];
       load8<T>(p, v);
       row = (long)b * cap + pos;
       if (col >= nq + nk) {
-        kind = 2;
+        kind = keep ? 2 : 0;
         cin = col - nq - nk;
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] = v[i];
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(256) void rope_append_fp8_kernel(T* __restrict__ qk
         if (col < nq) {
           store8<T>(p, o);
         } else {
-          kind = 1;
+          kind = keep ? 1 : 0;
           cin = col - nq;
 #pragma unroll
           for (int i = 0; i < 8; ++i) x[i] = rnd<T>(o[i]);  // what the 16-bit cache would hold
@@ -445,16 +450,17 @@ hipError_t pra_kv_quantize(int dtype, const void* k, const void* v, long ld, voi
 }
 
 hipError_t pra_rope_append_fp8(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
-                               float* k_scale, float* v_scale, int B, long ld, int Hq, int Hkv, int D, int cap,
+                               float* k_scale, float* v_scale, int B, int nt, long ld, int Hq, int Hkv, int D, int cap,
                                hipStream_t s) {
-  if (B <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 128) || ld % 8) return hipErrorInvalidValue;
-  const long items = (long)B * (Hq + 2 * Hkv) * D / 8;
+  if (B <= 0 || nt <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || (D != 64 && D != 128) || ld % 8)
+    return hipErrorInvalidValue;
+  const long items = (long)B * nt * (Hq + 2 * Hkv) * D / 8;
   long grid = (items + 255) / 256;
   if (grid > 2048) grid = 2048;
   PRA_DISPATCH_16BIT(dtype, T,
                      hipLaunchKernelGGL((pra::rope_append_fp8_kernel<T>), dim3((unsigned)grid), dim3(256), 0, s,
                                         (T*)qkv, (const float2*)tab, kv_len, (uint8_t*)k_cache, (uint8_t*)v_cache,
-                                        k_scale, v_scale, B, ld, Hq, Hkv, D, cap));
+                                        k_scale, v_scale, B, nt, ld, Hq, Hkv, D, cap));
   return hipGetLastError();
 }
 

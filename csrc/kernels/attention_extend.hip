@@ -32,6 +32,8 @@
 // kv_len[b] and T -- not of cap, the batch or the other lengths -- and come out with the same bits from run
 // to run. The two settings differ only in the order of the fp32 sums.
 // Compiled with -fno-honor-nans like attention_docs.hip: no NaN is formed.
+// The tile loop exists three times and is kept in step by hand: here, in attention_extend_split.hip and in
+// attention_extend_fp8.hip (both arms over an fp8 cache).
 #include "attn_common.h"
 #include "common.h"
 #include "attn_launch.h"

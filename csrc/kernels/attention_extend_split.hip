@@ -22,6 +22,8 @@
 // the same bits from run to run, and a sequence's output does not depend on cap or on the rest of the
 // batch. Against the single pass only the order of the fp32 sums differs.
 // Compiled with -fno-honor-nans like attention_extend.hip: no NaN is formed.
+// The tile loop, the wave fold and the partial store exist three times and are kept in step by hand: here, in
+// attention_extend.hip (the single pass) and in attention_extend_fp8.hip (both arms over an fp8 cache).
 #include "attn_common.h"
 #include "common.h"
 #include "attn_launch.h"
@@ -288,3 +290,28 @@ hipError_t extend_split(int dtype, const void* q, long ldq, const void* k_cache,
 
 }  // namespace attn
 }  // namespace pra
+
+// The merge of the key split alone (attention_extend_fp8.hip writes the same partials). extend_split above keeps its
+// own launch of the same kernel beside the chunk kernel's: the two instantiate in one lambda, and that fixes the
+// order of the kernels in the code object, which is kept as it was. ws_o [B][T][Hq][NC][D],
+// ws_ml [B][T][Hq][NC][2], NC = ceil(cap / kExtendChunk)
+extern "C" hipError_t pra_attn_extend_combine(int dtype, const float* ws_o, const float* ws_ml, const int* kv_len,
+                                              void* o, float* lse, int B, int T, int Hq, int D, int cap, int NC,
+                                              hipStream_t s) {
+  using namespace pra::attn;
+  const long nrows = (long)B * T * Hq;
+  if (ws_o == nullptr || ws_ml == nullptr || kv_len == nullptr || o == nullptr || lse == nullptr || nrows <= 0 ||
+      nrows > 0x7fffffffL || NC != (cap + kExtendChunk - 1) / kExtendChunk)
+    return hipErrorInvalidValue;
+  return dispatch_16bit(dtype, [&](auto t) {
+    using E = decltype(t);
+    const bool found = pra::dispatch(
+        [&](auto d) {
+          constexpr int RPB = 256 / (d() / 4);
+          hipLaunchKernelGGL((extend_combine_kernel<E, d()>), dim3((unsigned)((nrows + RPB - 1) / RPB)), dim3(256), 0,
+                             s, ws_o, ws_ml, kv_len, (E*)o, lse, nrows, T, Hq, cap, NC);
+        },
+        HeadDim{D});
+    return found ? hipGetLastError() : hipErrorInvalidValue;
+  });
+}

@@ -2,7 +2,7 @@
 
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
         --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
-        [--sampler philox --decode-graph] [--kv-cache-dtype fp8] [--prefill-chunk 512]
+        [--sampler philox --decode-graph] [--kv-cache-dtype fp8] [--prefill-chunk 512] [--fp8-extend]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
 ``--model-dtype``, ``--tokenizer-name-or-path``) and the checkpoint flags (``--checkpoint-dir``,
@@ -78,7 +78,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--prefill-chunk", type=int, default=0, metavar="N",
                    help="feed the prompt through in pieces of N tokens, each appended to the cache so far "
                         "(csrc/kernels/attention_extend.hip): the prefill's activation memory scales with N, not "
-                        "with the prompt. 0 (default): one pass over the whole prompt. Not with --kv-cache-dtype fp8")
+                        "with the prompt. 0 (default): one pass over the whole prompt. With --kv-cache-dtype fp8 "
+                        "it needs --fp8-extend")
+    p.add_argument("--fp8-extend", action="store_true",
+                   help="let --prefill-chunk run on an fp8 cache (csrc/kernels/attention_extend_fp8.hip): each "
+                        "piece is quantized into the cache first and attends to dequantized rows, as a decode step "
+                        "does, so the tokens differ from the one-shot prefill's by quantization error. Ignored "
+                        "for --kv-cache-dtype model")
     p.add_argument("--no-kv-cache", action="store_true",
                    help="naive path: a full forward over the whole prefix per new token (debugging aid)")
     p.add_argument("--output-jsonl", type=str, default=None,
@@ -113,7 +119,8 @@ def main(argv=None) -> int:
     tokens, reasons = generate(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                top_p=args.top_p, seed=args.seed, eos_id=eos, use_cache=not args.no_kv_cache,
                                stats=stats, sampler=args.sampler, graph=args.decode_graph,
-                               kv_cache_dtype=args.kv_cache_dtype, prefill_chunk=args.prefill_chunk)
+                               kv_cache_dtype=args.kv_cache_dtype, prefill_chunk=args.prefill_chunk,
+                               fp8_extend=args.fp8_extend)
     records = []
     for p, ids, why in zip(prompts, tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None

@@ -15,7 +15,9 @@ continuation after a shared prefix, a scoring or verification pass): the T-token
 A short append over a long cache runs its key-split arm (attention_extend_split.hip: fixed key chunks, fp32
 partials, an ordered combine) by a plan that reads shapes and the CU count only; see :func:`attention_extend`.
 ``prefill(chunk=N)`` feeds a prompt through it in pieces of N columns, so the prefill's activation memory
-is bounded by the piece. fp8 caches are refused by both.
+is bounded by the piece. Both refuse an fp8 cache unless ``fp8_extend=True``: then the new tokens are
+quantized into the cache first and every query attends to dequantized rows, as in ``decode_step``
+(csrc/kernels/attention_extend_fp8.hip, the T-token ``rope_append_fp8``).
 
 The HIP decode kernels take bf16 / fp16 at head_dim 64 / 128. CPU tensors, fp32 / fp64 models on the
 GPU and other head dims run the torch math of :mod:`pyrecover_amd.ops.reference`
@@ -102,11 +104,9 @@ def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None) 
     b * T + t has q rotated in place at position kv_len[b] + t, rotated k and plain v into that cache row.
     Bit-equal to ``rope_`` on the same row at that position. T = 1 clamps the row to cap - 1; with T > 1 a
     position at or beyond the capacity stores nothing (its q takes table row cap - 1).
-    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows are quantized on the way in
-    (T = 1 only)."""
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows, for any T, are quantized on
+    the way in -- the cache is a pure function of what the 16-bit cache would hold."""
     fp8 = k_scale is not None
-    if fp8 and qkv.shape[0] != k_cache.shape[0]:
-        raise ValueError("rope_append: an fp8 cache takes one token per sequence (extend does not serve fp8 caches)")
     if _decode_hip(qkv, k_cache.shape[-1]):
         C = _ext.require_for(qkv)
         if fp8:
@@ -140,8 +140,8 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     return o.to(q.dtype), lse
 
 
-def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
-                     split: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None, split: Optional[bool] = None,
+                     k_scale=None, v_scale=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, T, Hq, D] over the caches [B, cap, Hkv, D], which hold the T new tokens' k / v already
     (:func:`rope_append` first); ``kv_len`` [B] counts the tokens held before the append. Query t of
     sequence b attends to keys 0 .. min(kv_len[b] + t, cap - 1). Returns (o [B, T, Hq, D] in q's dtype,
@@ -153,13 +153,25 @@ def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     from device data -- the split for a short append over a long cache, where the single pass leaves most CUs
     idle. For a fixed setting a sequence's result is a pure function of its own q, K, V, ``kv_len[b]`` and T
     (not of cap, the batch or the other lengths) with the same bits run to run; the two settings differ only
-    in fp32 summation order. The torch-math path ignores it."""
+    in fp32 summation order. The torch-math path ignores it.
+
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8, the new rows quantized by :func:`rope_append`) and
+    the keys are their dequantized rows, a query's own row and the other new rows included:
+    csrc/kernels/attention_extend_fp8.hip, which converts the bytes once while staging them and is the 16-bit
+    kernel from there on. Same ``split``, same plan, same contract."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    fp8 = k_scale is not None
     if _decode_hip(q, q.shape[-1]):
-        o, lse = _ext.require_for(q).attn_extend(q, k_cache, v_cache, kv_len, scale,
-                                                 -1 if split is None else int(bool(split)))
+        C, sp = _ext.require_for(q), -1 if split is None else int(bool(split))
+        if fp8:
+            o, lse = C.attn_extend_fp8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, sp)
+        else:
+            o, lse = C.attn_extend(q, k_cache, v_cache, kv_len, scale, sp)
         return o, lse
-    o, lse = ref.attention_extend_ref(q, k_cache, v_cache, kv_len, scale)
+    if fp8:
+        o, lse = ref.attention_extend_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+    else:
+        o, lse = ref.attention_extend_ref(q, k_cache, v_cache, kv_len, scale)
     return o.to(q.dtype), lse
 
 
@@ -240,16 +252,19 @@ def _check_cache(model, cache: KVCache, B: int):
         raise ValueError("KVCache: an fp8 cache holds uint8 k / v and fp32 scales [B, capacity, Hkv]")
 
 
-def _refuse_fp8(cache: KVCache, what: str) -> None:
-    if getattr(cache, "fp8", False):
+def _refuse_fp8(cache: KVCache, what: str, fp8_extend: bool = False) -> None:
+    if getattr(cache, "fp8", False) and not fp8_extend:
         raise ValueError(f"{what} does not serve an fp8 KV cache: the prompt's attention is defined as unquantized "
-                         f"(prefill), and new tokens attending to their own dequantized keys would change that")
+                         f"(prefill), and new tokens attending to their own dequantized keys would change that. "
+                         f"Opt in with fp8_extend=True (generate.py --fp8-extend): the new tokens are quantized "
+                         f"into the cache first and every query attends to dequantized rows, as in decode_step")
 
 
 def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
     """tokens [B, T] through every layer as an append at ``cache.kv_len`` (left unchanged): per layer the QKV
     GEMM on [B * T, dim], the T-token ``rope_append``, ``attn_extend``, W_o and the MLP, with the rounding
-    points of ``decode_step``. Returns (h, pending) [B, T, dim] for :func:`_head`."""
+    points of ``decode_step``. An fp8 cache (the callers have checked the opt-in) passes its layer's scales to
+    both ops. Returns (h, pending) [B, T, dim] for :func:`_head`."""
     B, T = tokens.shape
     a = model.model_args
     Hq, Hkv, D = a.n_heads, a.kv_heads, a.head_dim
@@ -265,8 +280,10 @@ def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
             x, n1 = model._norm(layer.attention_norm, h, pending)
         at = layer.attention
         qkv = torch.mm(n1.reshape(B * T, n1.shape[-1]), model._weight(_qkv_params(at)).t())
-        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i])
-        o, _ = attention_extend(qkv[:, :nq].view(B, T, Hq, D), cache.k[i], cache.v[i], cache.kv_len, scale)
+        ks, vs = cache.k_scale[i], cache.v_scale[i]  # None for a cache in the model's dtype
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs)
+        o, _ = attention_extend(qkv[:, :nq].view(B, T, Hq, D), cache.k[i], cache.v[i], cache.kv_len, scale,
+                                k_scale=ks, v_scale=vs)
         att = F._mm_nt(o.view(B * T, nq), model._weight([at.wo.weight]), "o").view(B, T, -1)
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
@@ -274,7 +291,8 @@ def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
 
 
 @torch.no_grad()
-def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, return_all: bool = False) -> torch.Tensor:
+def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, return_all: bool = False,
+           fp8_extend: bool = False) -> torch.Tensor:
     """Append ``n_new[b]`` tokens (``tokens`` [B, T] right-padded, 1 <= n_new[b] <= T, values outside are
     clamped) to every sequence at its own ``kv_len[b]`` -> logits [B, V] of row n_new[b] - 1, the next
     position's; ``kv_len += n_new`` (clamped at the capacity). A follow-up turn, a continuation after a
@@ -285,12 +303,17 @@ def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, ret
     beyond the capacity stores nothing and attends to the whole cache (T = 1 overwrites the last row, as
     ``decode_step`` does). ``n_new`` and ``kv_len`` stay on the device: no host synchronisation.
     ``return_all=True`` returns the logits of every row, [B, T, V], instead (scoring; pad rows included).
-    fp8 caches are refused with ``ValueError``."""
+
+    An fp8 cache is refused with ``ValueError`` unless ``fp8_extend=True``. With it an append does, per layer,
+    what ``decode_step`` does for one token: the T new tokens' rotated k and plain v are quantized into the
+    cache first, then query t attends to the dequantized cache rows 0 .. min(kv_len[b] + t, cap - 1), its own
+    row and the other new rows included. So ``extend`` with T = 1 is ``decode_step``, and with T tokens it
+    equals T ``decode_step`` calls in exact arithmetic. The flag is ignored for a cache in the model's dtype."""
     if tokens.dim() != 2 or tokens.shape[1] < 1:
         raise ValueError(f"extend: tokens must be [B, T] with T >= 1, got {tuple(tokens.shape)}")
     B, T = tokens.shape
     _check_cache(model, cache, B)
-    _refuse_fp8(cache, "extend")
+    _refuse_fp8(cache, "extend", fp8_extend)
     n_new = n_new.to(device=tokens.device, dtype=torch.long).clamp(1, T)
     h, pending = _extend_layers(model, tokens, cache)
     cache.kv_len.copy_((cache.kv_len + n_new).clamp(max=cache.capacity))
@@ -325,7 +348,8 @@ def _prefill_chunked(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVC
 
 
 @torch.no_grad()
-def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chunk: int = 0) -> torch.Tensor:
+def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chunk: int = 0,
+            fp8_extend: bool = False) -> torch.Tensor:
     """tokens [B, S] (ragged prompts right-padded), lens [B] in 1 .. S -> logits [B, V] of row
     lens[b] - 1 of each sequence. Fills the cache rows 0 .. S - 1 and sets kv_len = lens. Causal
     attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist.
@@ -338,7 +362,9 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     ``chunk > 0`` feeds the prompt in pieces of ``chunk`` columns, each an append onto the cache so far
     (the layer body of :func:`extend`): peak activation memory scales with B * chunk, not B * S, and the
     result is the one-shot prefill's up to summation order. It refuses an fp8 cache (``ValueError``): a
-    piece would attend to dequantized keys. ``chunk = 0`` is the one-shot path."""
+    piece would attend to dequantized keys. ``fp8_extend=True`` opts into exactly that (see :func:`extend`):
+    every piece attends to dequantized rows, so the result differs from the one-shot prefill by quantization
+    error, not only by summation order. ``chunk = 0`` is the one-shot path, with or without the flag."""
     B, S = tokens.shape
     _check_cache(model, cache, B)
     if S > cache.capacity:
@@ -347,7 +373,7 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     if chunk < 0:
         raise ValueError(f"prefill: chunk must be >= 0, got {chunk}")
     if chunk > 0:
-        _refuse_fp8(cache, "prefill(chunk > 0)")
+        _refuse_fp8(cache, "prefill(chunk > 0)", fp8_extend)
         return _prefill_chunked(model, tokens, lens, cache, int(chunk))
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens, emb, model._slot([emb]))
@@ -557,7 +583,8 @@ def _graph_refusal(model, device, dtype, sampler: str, temperature: float, use_c
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
              stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
-             kv_cache_dtype: str = "model", prefill_chunk: int = 0) -> Tuple[List[List[int]], List[str]]:
+             kv_cache_dtype: str = "model", prefill_chunk: int = 0,
+             fp8_extend: bool = False) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -585,8 +612,10 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
 
     ``prefill_chunk=N`` (N > 0) feeds the prompt through :func:`prefill` in pieces of N columns, bounding the
     prefill's activation memory by B * N rows; the tokens are those of the one-shot prefill up to summation
-    order. It needs the cache and refuses ``kv_cache_dtype="fp8"``. ``stats["prefill_chunks"]`` is the number
-    of pieces (0: the one-shot prefill)."""
+    order. It needs the cache and refuses ``kv_cache_dtype="fp8"`` unless ``fp8_extend=True``: then every piece
+    attends to dequantized cache rows (:func:`extend`), and the tokens differ from the one-shot prefill's by
+    quantization error too. The flag does nothing for a ``"model"`` cache. ``stats["prefill_chunks"]`` is the
+    number of pieces (0: the one-shot prefill)."""
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
     if sampler not in ("torch", "philox"):
@@ -628,7 +657,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     timer.mark()
     if use_cache:
         cache = KVCache(args, B, cap, dtype, device, kv_cache_dtype)
-        logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk)
+        logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk, fp8_extend=fp8_extend)
     else:
         bi = torch.arange(B, device=device)
         logits = model(buf[:, :S])[bi, lens - 1]

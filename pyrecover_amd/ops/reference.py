@@ -315,9 +315,10 @@ def kv_dequantize_ref(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype =
 
 
 def rope_append_fp8_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale) -> None:
-    """:func:`rope_append_ref` over an fp8 cache: q is rotated in place as there; the k row is rotated in
-    opmath, rounded once to qkv's dtype and then quantized, the v row quantized from its values: the cache
-    is a pure function of what the 16-bit cache would hold."""
+    """:func:`rope_append_ref` over an fp8 cache, T tokens per sequence with its rows and its overflow rule
+    (T = 1 clamps the row to cap - 1, T > 1 stores nothing at or beyond cap): q is rotated in place as there;
+    the k row is rotated in opmath, rounded once to qkv's dtype and then quantized, the v row quantized from its
+    values: the cache is a pure function of what the 16-bit cache would hold."""
     bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, *k_cache.shape)
     k_cache[bi, pos], k_scale[bi, pos] = kv_quantize_ref(k)
     v_cache[bi, pos], v_scale[bi, pos] = kv_quantize_ref(v)
@@ -327,6 +328,15 @@ def attention_decode_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scal
     """:func:`attention_decode_ref` on the dequantized cache, in q's precision promoted to at least fp32."""
     dt = up(q).dtype
     return attention_decode_ref(q, kv_dequantize_ref(k_cache, k_scale, dt), kv_dequantize_ref(v_cache, v_scale, dt),
+                                kv_len, scale)
+
+
+def attention_extend_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale: Optional[float] = None):
+    """:func:`attention_extend_ref` on the dequantized cache, in q's precision promoted to at least fp32 (HIP:
+    csrc/kernels/attention_extend_fp8.hip). The caches hold the T new tokens' quantized rows already; whatever
+    bytes and scales lie beyond a row's bound (NaN and Inf included) never reach its output."""
+    dt = up(q).dtype
+    return attention_extend_ref(q, kv_dequantize_ref(k_cache, k_scale, dt), kv_dequantize_ref(v_cache, v_scale, dt),
                                 kv_len, scale)
 
 

@@ -117,11 +117,13 @@ def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
     return hip, tor
 
 
-def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1):
+def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model",)):
     """``attn_extend`` alone: T new queries per sequence over a cache of capacity ctx that held ``base`` keys
     before the append (default ctx - T: the append fills the cache). With base 0 the call is a causal forward,
     and the document-masked forward (one document per row) is timed at the same shape beside it. ``split``:
-    -1 by plan, 0 the single pass, 1 the key split."""
+    -1 by plan, 0 the single pass, 1 the key split. With "fp8" in ``kinds`` the same caches, quantized, are timed
+    through ``attn_extend_fp8`` in the same process (same plan, same rotation). With more than one arm (fp8,
+    docs_fwd) the arms alternate over three rounds; every round's time is printed, the median is the headline."""
     C = _ext.native()
     Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
     base = ctx - T if base is None else base
@@ -135,7 +137,30 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1):
     n = torch.full((B,), base, device=dev, dtype=torch.int32)
     scale = 1 / math.sqrt(D)
     flop = 4.0 * B * Hq * D * sum(base + t + 1 for t in range(T))  # q.k and p.v over the visible keys
-    hip = timed_us(lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale, split), iters)
+    # Arms of one shape alternate inside a round and the round repeats (3 rounds when there is more than one
+    # arm): the first timing of a process runs slow, and a later arm otherwise inherits a warmer machine.
+    arms = [("16", lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale, split))]
+    c8 = []
+    if "fp8" in kinds:
+        for k, v in zip(ks, vs):
+            kq, vq = torch.empty_like(k, dtype=torch.uint8), torch.empty_like(v, dtype=torch.uint8)
+            sk, sv = (torch.empty(B, ctx, Hkv, device=dev) for _ in range(2))
+            C.kv_quantize_(k, v, kq, vq, sk, sv)
+            c8.append((kq, vq, sk, sv))
+        arms.append(("fp8", lambda i: C.attn_extend_fp8(q, *c8[i % n_buf], n, scale, split)))
+    with_docs = base == 0 and T % 128 == 0
+    if with_docs:
+        ds = torch.zeros(B, T, dtype=torch.int32, device=dev)
+        kk, vv = [k[:, :T] for k in ks], [v[:, :T] for v in vs]
+        arms.append(("docs", lambda i: C.attn_fwd(q, kk[i % n_buf], vv[i % n_buf], scale, True, ds)))
+    rounds = 3 if len(arms) > 1 else 1
+    times = {a: [] for a, _ in arms}
+    for _ in range(rounds):
+        for a, fn in arms:
+            times[a].append(timed_us(fn, iters))
+    med = {a: sorted(t)[len(t) // 2] for a, t in times.items()}
+    every = {a: " ".join(f"{x:.1f}" for x in t) for a, t in times.items()}
+    hip = med["16"]
     o, _ = C.attn_extend(q, ks[0], vs[0], n, scale, split)
     on = C.attn_extend_plan(B, T, Hq, Hkv, D, ctx)["split"] if split < 0 else bool(split)
     R, XC = T * (Hq // Hkv), C.attn_extend_chunk()
@@ -145,23 +170,34 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1):
     print(f"{name}: attn_extend B={B} T={T} over kv_len={base} (cap {ctx}) Hq/Hkv={Hq}/{Hkv} D={D}: "
           f"{'plan: ' if split < 0 else ''}{arm}, {blocks} blocks, "
           f"{per_layer / 2**20:.0f} MiB of K/V, {n_buf} caches in rotation")
-    print(f"  HIP   {hip:9.1f} us  {flop / hip / 1e6:7.1f} TFLOP/s  {per_layer / hip / 1e6:6.2f} TB/s of K/V read once")
+    print(f"  HIP   {hip:9.1f} us  {flop / hip / 1e6:7.1f} TFLOP/s  {per_layer / hip / 1e6:6.2f} TB/s of K/V read once"
+          + (f"  (median of rounds: {every['16']})" if rounds > 1 else ""))
     if T * B * ctx <= 1 << 24:  # the oracle materialises [B, T, Hq, ctx] scores
         o_ref, _ = ref.attention_extend_ref(q.float(), ks[0].float(), vs[0].float(), n, scale)
         print(f"  max |o - o_ref| {(o.float() - o_ref).abs().max().item():.2e}")
-    if base == 0 and T % 128 == 0:
-        ds = torch.zeros(B, T, dtype=torch.int32, device=dev)
-        kk, vv = [k[:, :T] for k in ks], [v[:, :T] for v in vs]
-        docs = timed_us(lambda i: C.attn_fwd(q, kk[i % n_buf], vv[i % n_buf], scale, True, ds), iters)
+    if c8:
+        per8, hip8 = per_layer // 2 // D * (D + 4), med["fp8"]
+        print(f"  HIP fp8 {hip8:7.1f} us  {flop / hip8 / 1e6:7.1f} TFLOP/s  {per8 / hip8 / 1e6:6.2f} TB/s of "
+              f"{per8 / 2**20:.0f} MiB (bytes and scales): {hip / hip8:.2f}x of the 16-bit call  "
+              f"(median of rounds: {every['fp8']})")
+        if T * B * ctx <= 1 << 24:
+            o8, _ = C.attn_extend_fp8(q, *c8[0], n, scale, split)
+            kd, vd = (ref.kv_dequantize_ref(c8[0][j], c8[0][j + 2]) for j in (0, 1))
+            o_ref, _ = ref.attention_extend_ref(q.float(), kd, vd, n, scale)
+            print(f"  max |o - o_ref(dequantized)| {(o8.float() - o_ref).abs().max().item():.2e}")
+    if with_docs:
+        docs = med["docs"]
         od, _ = C.attn_fwd(q, kk[0], vv[0], scale, True, ds)
         print(f"  docs_fwd, one document per row, same shape: {docs:9.1f} us  {flop / docs / 1e6:7.1f} TFLOP/s "
-              f"(attn_extend takes {hip / docs:.2f}x; max |o - o_docs| {(o.float() - od.float()).abs().max().item():.2e})")
+              f"(attn_extend takes {hip / docs:.2f}x; max |o - o_docs| {(o.float() - od.float()).abs().max().item():.2e}"
+              f"; rounds: {every['docs']})")
     return hip
 
 
-def bench_prefill(name, preset, B, S, layers, chunks, iters, dev):
+def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="model"):
     """``prefill`` of a B x S prompt, one-shot (chunk 0) and in pieces: milliseconds and the peak of
-    ``torch.cuda.max_memory_allocated`` above what the model and the cache hold."""
+    ``torch.cuda.max_memory_allocated`` above what the model and the cache hold. An fp8 cache takes the pieces
+    with ``fp8_extend=True``."""
     cfg = get_preset(preset, n_layers=layers, seq_len=S)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
@@ -170,20 +206,20 @@ def bench_prefill(name, preset, B, S, layers, chunks, iters, dev):
     torch.set_default_dtype(prev)
     model.eval()
     model.flatten_(shadows=False)
-    cache = inf.KVCache(cfg, B, S, torch.bfloat16, dev)
+    cache = inf.KVCache(cfg, B, S, torch.bfloat16, dev, kv_dtype=kv_dtype)
     tok = torch.randint(0, cfg.vocab_size, (B, S), device=dev)
     lens = torch.full((B,), S, device=dev)
-    print(f"{name}: prefill of B={B} x S={S}, {layers} layers, bf16 (model + cache "
+    print(f"{name}: prefill of B={B} x S={S}, {layers} layers, bf16, {kv_dtype} cache (model + cache "
           f"{torch.cuda.memory_allocated() / 2**30:.2f} GiB resident)")
     first = None
     for c in chunks:
-        inf.prefill(model, tok, lens, cache, chunk=c)  # library warm-up and GEMM tuning at this piece's shapes
+        inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True)  # library warm-up and GEMM tuning at this piece's shapes
         torch.cuda.synchronize()
         resident = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
-        us = timed_us(lambda _: inf.prefill(model, tok, lens, cache, chunk=c), iters, 1)
+        us = timed_us(lambda _: inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True), iters, 1)
         peak = torch.cuda.max_memory_allocated() - resident
-        logits = inf.prefill(model, tok, lens, cache, chunk=c).float()
+        logits = inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True).float()
         first = logits if first is None else first
         print(f"  chunk {c:5d}: prefill_ms {us / 1e3:9.2f}  peak activations {peak / 2**30:7.3f} GiB  "
               f"max |logits - logits(chunk {chunks[0]})| {(logits - first).abs().max().item():.3e}")
@@ -345,12 +381,13 @@ def main():
     if a.extend:
         for name, preset, B, ctx in shapes:
             bench_extend(name, get_preset(preset), B, ctx, a.extend, a.extend_base, a.iters, dev,
-                         -1 if a.extend_split == "auto" else int(a.extend_split))
+                         -1 if a.extend_split == "auto" else int(a.extend_split), kinds)
         return
     if a.prefill:
         for name, preset, B, _ in shapes:
-            bench_prefill(name, preset, B, a.prefill, a.layers, [int(c) for c in a.prefill_chunk.split(",")],
-                          max(3, a.iters // 10), dev)
+            for kind in kinds:
+                bench_prefill(name, preset, B, a.prefill, a.layers, [int(c) for c in a.prefill_chunk.split(",")],
+                              max(3, a.iters // 10), dev, kind)
         return
     if a.sampler or a.graph:
         samplers = ("torch", "philox") if a.sampler == "both" else (a.sampler,) if a.sampler else ()
