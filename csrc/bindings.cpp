@@ -1232,6 +1232,162 @@ std::vector<at::Tensor> attn_decode_fp8(const at::Tensor& q, const at::Tensor& k
   return {o, lse};
 }
 
+// Paged KV cache (csrc/kernels/attention_paged.hip): the checks of check_decode_common with pools
+// [n_pages, page, Hkv, D] (page 64 / 128 / 256), the logical capacity `cap` and the block table int32
+// [B, ceil(cap / page)] on the reference tensor's device. kv_len: absent for the prompt store.
+void check_paged_common(const at::Tensor& ref, const at::Tensor& kp, const at::Tensor& vp, const at::Tensor& bt,
+                        const at::Tensor* kv_len, int64_t B, int64_t cap, const char* op) {
+  TORCH_CHECK(ref.scalar_type() == at::kBFloat16 || ref.scalar_type() == at::kHalf, op,
+              ": the HIP kernels take bf16 or fp16 (got ", ref.scalar_type(),
+              "); other dtypes run the torch math of pyrecover_amd.ops.reference");
+  same_dev(ref, kp, "k_pool");
+  same_dev(ref, vp, "v_pool");
+  same_dev(ref, bt, "block_table");
+  TORCH_CHECK(kp.dim() == 4 && kp.size(0) > 0 && kp.size(2) > 0, op,
+              ": k_pool must be [n_pages, page, Hkv, D], got ", kp.sizes());
+  TORCH_CHECK(vp.sizes() == kp.sizes(), op, ": v_pool must have k_pool's shape");
+  TORCH_CHECK(kp.is_contiguous() && vp.is_contiguous(), op, ": the pools must be contiguous");
+  TORCH_CHECK(kp.scalar_type() == ref.scalar_type() && vp.scalar_type() == ref.scalar_type(), op,
+              ": the pools must have the query's dtype");
+  const int64_t page = kp.size(1);
+  TORCH_CHECK(page == 64 || page == 128 || page == 256, op, ": the page size must be 64, 128 or 256, got ", page);
+  TORCH_CHECK(kp.size(3) == 64 || kp.size(3) == 128, op, ": head_dim must be 64 or 128");
+  TORCH_CHECK(cap > 0 && cap <= (int64_t)INT32_MAX / 2 && kp.size(0) * page <= (int64_t)INT32_MAX &&
+                  kp.size(2) <= 65535 && B > 0 && B <= 65535,
+              op, ": bad shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(kp.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(vp.data_ptr()) % 16 == 0,
+              op, ": the pools must be 16-B aligned");
+  TORCH_CHECK(bt.scalar_type() == at::kInt && bt.dim() == 2 && bt.size(0) == B &&
+                  bt.size(1) == (cap + page - 1) / page && bt.is_contiguous(),
+              op, ": block_table must be contiguous int32 [B, ceil(cap / page)] = [", B, ", ", (cap + page - 1) / page,
+              "], got ", bt.scalar_type(), " ", bt.sizes());
+  if (kv_len != nullptr) {
+    same_dev(ref, *kv_len, "kv_len");
+    TORCH_CHECK(kv_len->scalar_type() == at::kInt && kv_len->dim() == 1 && kv_len->size(0) == B &&
+                    kv_len->is_contiguous(),
+                op, ": kv_len must be contiguous int32 [B]");
+  }
+}
+
+// rope_append_ over a paged cache: B is the table's; the rows and the overflow rule of rope_append_, a token on
+// an unmapped page stores nothing (its q is still rotated).
+void rope_append_paged_(at::Tensor qkv, const at::Tensor& tab, const at::Tensor& kv_len, at::Tensor k_pool,
+                        at::Tensor v_pool, const at::Tensor& block_table, int64_t cap) {
+  const Range range_("pyrecover::rope_append_paged");
+  check_dev(qkv, "qkv");
+  check_row_major(qkv, "rope_append_paged qkv");
+  const int64_t B = block_table.dim() == 2 ? block_table.size(0) : qkv.size(0);
+  check_paged_common(qkv, k_pool, v_pool, block_table, &kv_len, B, cap, "rope_append_paged");
+  const int64_t page = k_pool.size(1), Hkv = k_pool.size(2), D = k_pool.size(3);
+  TORCH_CHECK(qkv.size(0) > 0 && qkv.size(0) % B == 0 && qkv.size(0) / B <= (int64_t)INT32_MAX / 2,
+              "rope_append_paged: qkv must hold T rows for each of the table's B = ", B, " sequences, got ", qkv.sizes());
+  const int64_t T = qkv.size(0) / B;
+  TORCH_CHECK(qkv.size(1) % D == 0 && qkv.size(1) / D > 2 * Hkv && (qkv.size(1) / D - 2 * Hkv) % Hkv == 0,
+              "rope_append_paged: qkv must be [B, (Hq + 2 Hkv) D] with Hq a multiple of Hkv, got ", qkv.sizes());
+  TORCH_CHECK(qkv.stride(0) % 8 == 0, "rope_append_paged: the qkv row stride must be a multiple of 8 elements");
+  const int64_t Hq = qkv.size(1) / D - 2 * Hkv;
+  same_dev(qkv, tab, "rope table");
+  TORCH_CHECK(tab.scalar_type() == at::kFloat && tab.is_contiguous() && tab.dim() == 3 && tab.size(0) >= cap &&
+                  tab.size(1) == D / 2 && tab.size(2) == 2,
+              "rope_append_paged: table must be contiguous fp32 [>= cap, D/2, 2]");
+  const c10::DeviceGuard guard(qkv.device());
+  check(pra_rope_append_paged(dt(qkv), qkv.data_ptr(), tab.data_ptr(), kv_len.data_ptr<int>(), k_pool.data_ptr(),
+                              v_pool.data_ptr(), block_table.data_ptr<int>(), (int)B, (int)T, qkv.stride(0), (int)Hq,
+                              (int)Hkv, (int)D, (int)cap, (int)page, (int)k_pool.size(0), stream_of(qkv)),
+        "rope_append_paged");
+}
+
+// k, v [B, S, Hkv, D]: the k and v views of the fused QKV activation [B * S, ld] into logical rows 0 .. S - 1
+// of the paged cache; rows on unmapped pages are skipped.
+void kv_store_paged_(const at::Tensor& k, const at::Tensor& v, at::Tensor k_pool, at::Tensor v_pool,
+                     const at::Tensor& block_table, int64_t cap) {
+  const Range range_("pyrecover::kv_store_paged");
+  check_dev(k, "k");
+  TORCH_CHECK(k.dim() == 4, "kv_store_paged: k must be [B, S, Hkv, D], got ", k.sizes());
+  const int64_t B = k.size(0), S = k.size(1), Hkv = k.size(2), D = k.size(3);
+  check_paged_common(k, k_pool, v_pool, block_table, nullptr, B, cap, "kv_store_paged");
+  same_dev(k, v, "v");
+  TORCH_CHECK(v.sizes() == k.sizes() && v.scalar_type() == k.scalar_type() && v.strides() == k.strides(),
+              "kv_store_paged: v must have k's shape, dtype and strides");
+  TORCH_CHECK(k_pool.size(2) == Hkv && k_pool.size(3) == D, "kv_store_paged: k and the pools disagree on [Hkv, D]");
+  TORCH_CHECK(S > 0 && S <= cap, "kv_store_paged: ", S, " rows do not fit the cache capacity ", cap);
+  const int64_t ld = k.stride(1);
+  TORCH_CHECK(k.stride(3) == 1 && k.stride(2) == D && ld >= Hkv * D && ld % 8 == 0 && (B == 1 || k.stride(0) == S * ld),
+              "kv_store_paged: k and v must be [B, S, Hkv, D] views of rows [B * S, ld] with ld a multiple of 8 elements");
+  TORCH_CHECK(B * S <= (int64_t)INT32_MAX / 2, "kv_store_paged: bad shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(k.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(v.data_ptr()) % 16 == 0,
+              "kv_store_paged: k and v must be 16-B aligned");
+  const c10::DeviceGuard guard(k.device());
+  check(pra_kv_store_paged(dt(k), k.data_ptr(), v.data_ptr(), ld, k_pool.data_ptr(), v_pool.data_ptr(),
+                           block_table.data_ptr<int>(), (int)B, (int)S, (int)Hkv, (int)D, (int)cap, (int)k_pool.size(1),
+                           (int)k_pool.size(0), stream_of(k)),
+        "kv_store_paged");
+}
+
+// attn_decode over a paged cache -> (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq]).
+std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                          const at::Tensor& block_table, const at::Tensor& kv_len, int64_t cap,
+                                          double scale) {
+  const Range range_("pyrecover::attn_decode_paged");
+  check_dev(q, "q");
+  TORCH_CHECK(q.dim() == 3, "attn_decode_paged: q must be [B, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  check_paged_common(q, k_pool, v_pool, block_table, &kv_len, B, cap, "attn_decode_paged");
+  const int64_t Hkv = k_pool.size(2);
+  TORCH_CHECK(k_pool.size(3) == D, "attn_decode_paged: q and the pools disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_decode_paged: n_heads must be a multiple of n_kv_heads");
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_decode_paged: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, Hq}, q.options().dtype(at::kFloat));
+  at::Tensor ws = at::empty({pra_attn_decode_ws_floats((int)B, (int)Hq, (int)D, (int)cap)},
+                            q.options().dtype(at::kFloat));
+  check(pra_attn_decode_paged(dt(q), qc.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), block_table.data_ptr<int>(),
+                              kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(), ws.data_ptr<float>(), (int)B,
+                              (int)Hq, (int)Hkv, (int)D, (int)cap, (int)k_pool.size(1), (int)k_pool.size(0),
+                              (float)scale, stream_of(q)),
+        "attn_decode_paged");
+  return {o, lse};
+}
+
+// attn_extend over a paged cache, which holds the T new tokens already -> (o [B, T, Hq, D], lse fp32 [B, T, Hq]).
+// split and the workspace as attn_extend.
+std::vector<at::Tensor> attn_extend_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
+                                          const at::Tensor& block_table, const at::Tensor& kv_len, int64_t cap,
+                                          double scale, int64_t split) {
+  const Range range_("pyrecover::attn_extend_paged");
+  check_dev(q, "q");
+  TORCH_CHECK(split >= -1 && split <= 1, "attn_extend_paged: split must be -1 (by shape), 0 or 1, got ", split);
+  TORCH_CHECK(q.dim() == 4 && q.size(1) > 0, "attn_extend_paged: q must be [B, T, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  check_paged_common(q, k_pool, v_pool, block_table, &kv_len, B, cap, "attn_extend_paged");
+  const int64_t Hkv = k_pool.size(2);
+  TORCH_CHECK(k_pool.size(3) == D, "attn_extend_paged: q and the pools disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_extend_paged: n_heads must be a multiple of n_kv_heads");
+  TORCH_CHECK(T * (Hq / Hkv) <= (int64_t)INT32_MAX / 2, "attn_extend_paged: bad shape");
+  int64_t ldq = T > 1 ? q.stride(1) : B > 1 ? q.stride(0) : Hq * D;  // a dim of size 1 has no stride to speak of
+  const bool view_ok = q.stride(3) == 1 && q.stride(2) == D && ldq % 8 == 0 && ldq >= Hq * D &&
+                       (B == 1 || q.stride(0) == T * ldq);
+  at::Tensor qc = view_ok ? q : q.contiguous();
+  if (!view_ok) ldq = Hq * D;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_extend_paged: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, T, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, T, Hq}, q.options().dtype(at::kFloat));
+  pra_attn_extend_plan_t pl;
+  pra_attn_extend_plan((int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap, (int)split, &pl);
+  at::Tensor ws;
+  if (pl.split) ws = at::empty({pl.ws_floats}, q.options().dtype(at::kFloat));
+  check(pra_attn_extend_paged(dt(q), qc.data_ptr(), ldq, k_pool.data_ptr(), v_pool.data_ptr(),
+                              block_table.data_ptr<int>(), kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(),
+                              pl.split ? ws.data_ptr<float>() : nullptr, (int)B, (int)T, (int)Hq, (int)Hkv, (int)D,
+                              (int)cap, (int)k_pool.size(1), (int)k_pool.size(0), (float)scale, (int)split,
+                              stream_of(q)),
+        "attn_extend_paged");
+  return {o, lse};
+}
+
 // Device-side sampling (csrc/kernels/sample.hip): logits [B, V] bf16 / fp16 (row stride >= V) -> tok int64 [B].
 // temperature 0 is greedy; otherwise pos (int32 [B]) or, with the generation state, prompt_len + count
 // indexes the Philox draw. ws: int32 workspace of sample_ws_bytes(B) bytes (allocated here when absent).
@@ -1460,6 +1616,14 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_decode_fp8_chunk", []() { return pra_attn_decode_fp8_chunk(); });
   m.def("attn_extend_fp8", &attn_extend_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"), py::arg("split") = -1);
+  m.def("rope_append_paged_", &rope_append_paged_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_pool"),
+        py::arg("v_pool"), py::arg("block_table"), py::arg("cap"));
+  m.def("kv_store_paged_", &kv_store_paged_, py::arg("k"), py::arg("v"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("cap"));
+  m.def("attn_decode_paged", &attn_decode_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("kv_len"), py::arg("cap"), py::arg("scale"));
+  m.def("attn_extend_paged", &attn_extend_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("kv_len"), py::arg("cap"), py::arg("scale"), py::arg("split") = -1);
   m.def("sample_", &sample_, py::arg("logits"), py::arg("tok"), py::arg("temperature"), py::arg("top_k"),
         py::arg("top_p"), py::arg("seed"), py::arg("pos") = py::none(), py::arg("ws") = py::none(),
         py::arg("u_out") = py::none(), py::arg("done") = py::none(), py::arg("count") = py::none(),

@@ -211,6 +211,35 @@ int pra_attn_extend_chunk();
 hipError_t pra_attn_extend_combine(int dtype, const float* ws_o, const float* ws_ml, const int* kv_len, void* o,
                                    float* lse, int B, int T, int Hq, int D, int cap, int NC, hipStream_t s);
 
+// Paged KV cache (attention_paged.hip), bf16 / fp16, D 64 or 128. Per layer k_pool, v_pool are
+// [n_pages][page][Hkv][D] contiguous with page 64, 128 or 256 (every other value: hipErrorInvalidValue);
+// block_table is int32 [B][P] on the device, P = ceil(cap / page), cap the logical capacity with the meaning
+// it has above (no multiple of page needed). Logical key j of sequence b is row j % page of page
+// block_table[b][j / page]; one table serves all layers and two sequences may name the same page. An entry
+// < 0 or >= n_pages is unmapped: a store to it stores nothing, a load from it yields zeros and the key is
+// masked, and no address is formed from it. kv_len is clamped as above; neither it nor the table is read on
+// the host. Each launcher is its dense counterpart on the gathered cache
+// k[b][j] = k_pool[block_table[b][j / page]][j % page], bit for bit (pra_attn_extend_paged: at the same split),
+// whichever physical pages are used and whatever the rest of the pool holds; arguments, plan and workspaces
+// (pra_attn_decode_ws_floats, pra_attn_extend_ws_floats) are the dense ones.
+// rope_append_paged: the rows and the T = 1 / T > 1 overflow rule of pra_rope_append; a token whose page is
+// unmapped stores nothing and its q is still rotated. kv_store_paged: the k, v views [B * S][ld] of the fused
+// QKV activation (Hkv * D columns each, ld % 8 == 0) into logical rows 0 .. S - 1 (S <= cap), rows on unmapped
+// pages skipped.
+hipError_t pra_rope_append_paged(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_pool, void* v_pool,
+                                 const int* block_table, int B, int nt, long ld, int Hq, int Hkv, int D, int cap,
+                                 int page, int n_pages, hipStream_t s);
+hipError_t pra_kv_store_paged(int dtype, const void* k, const void* v, long ld, void* k_pool, void* v_pool,
+                              const int* block_table, int B, int S, int Hkv, int D, int cap, int page, int n_pages,
+                              hipStream_t s);
+hipError_t pra_attn_decode_paged(int dtype, const void* q, const void* k_pool, const void* v_pool,
+                                 const int* block_table, const int* kv_len, void* o, float* lse, float* ws, int B,
+                                 int Hq, int Hkv, int D, int cap, int page, int n_pages, float scale, hipStream_t s);
+hipError_t pra_attn_extend_paged(int dtype, const void* q, long ldq, const void* k_pool, const void* v_pool,
+                                 const int* block_table, const int* kv_len, void* o, float* lse, float* ws, int B, int T,
+                                 int Hq, int Hkv, int D, int cap, int page, int n_pages, float scale, int split,
+                                 hipStream_t s);
+
 // fp8 KV cache (attention_decode_fp8.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D] of
 // e4m3fn bytes, k_scale, v_scale fp32 [B][cap][Hkv], powers of two. dtype is the 16-bit type of qkv / q / o.
 // D 64 or 128. kv_quantize: k, v [B * S][ld] views of the fused QKV activation (Hkv * D columns each,

@@ -30,6 +30,12 @@ reads: csrc/kernels/attention_decode_fp8.hip (``kv_quantize``, ``rope_append_fp8
 rule in ``ops/reference.py::kv_quantize_ref``. The prompt's attention stays unquantized; only what is stored
 is quantized. Opt-in: without it nothing changes.
 
+:class:`PagedKVCache` (``generate(kv_page_size=N)``) keeps k / v in a pool of pages of 64, 128 or 256 tokens with
+one block table per batch: a sequence pays for the pages it reserved instead of ``capacity`` rows, and a shared
+prefix is shared pages (:meth:`PagedKVCache.share_prefix`). ``prefill``, ``extend``, the chunked prefill,
+``decode_step`` and :class:`DecodeGraph` take either cache; with a paged one the four cache ops run the page-walking
+kernels of csrc/kernels/attention_paged.hip, which return the dense kernels' bits. Opt-in: the default is dense.
+
 Sampling has two rules. ``sampler="torch"`` (the default) filters with ``torch.topk`` / ``torch.sort`` and
 draws with ``torch.multinomial`` from a seeded ``torch.Generator``. ``sampler="philox"`` is the stateless
 rule of csrc/kernels/sample.hip (:func:`sample_philox`): the uniform of a draw is a Philox function of
@@ -95,19 +101,144 @@ class KVCache:
         return n + 2 * self._k_scale.numel() * 4 if self.fp8 else n
 
 
+PAGE_SIZES = (64, 128, 256)  # divide the decode chunk (256) and the extend chunk (512); multiples of the 64-key tile
+
+
+class PagedKVCache:
+    """A KV cache in pages: per layer ``k[i]`` / ``v[i]`` are pools [n_pages, page_size, Hkv, D] and one int32
+    ``block_table`` [B, ceil(capacity / page_size)] on the device (shared by all layers, -1: unmapped) maps the
+    logical position j of sequence b to row ``j % page_size`` of page ``block_table[b, j // page_size]``
+    (csrc/kernels/attention_paged.hip). ``capacity`` is the logical capacity, with :class:`KVCache`'s meaning
+    and rule; ``kv_len`` is the same int32 device tensor. A sequence pays for the pages it reserved, not for
+    ``capacity`` rows, and two sequences may name the same page (:meth:`share_prefix`).
+
+    The allocator lives on the host: a free list and a reference count per page. :meth:`reserve` /
+    :meth:`release` / :meth:`share_prefix` push a changed table row with one small host-to-device copy; call
+    them outside a captured region and before a decode loop, never inside one (``generate`` reserves every
+    sequence's pages before the prefill, so the table is static while decoding). ``n_pages`` defaults to
+    ``batch * ceil(capacity / page_size)``, the dense cache's footprint. A paged fp8 cache is a follow-up."""
+
+    fp8 = False
+    kv_dtype = "model"
+
+    def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device,
+                 page_size: int = 128, n_pages: Optional[int] = None, kv_dtype: str = "model"):
+        if kv_dtype != "model":
+            raise ValueError(f"PagedKVCache: kv_dtype={kv_dtype!r} is not served: a paged fp8 cache is a follow-up")
+        if page_size not in PAGE_SIZES:
+            raise ValueError(f"PagedKVCache: page_size must be one of {PAGE_SIZES}, got {page_size}")
+        if capacity > model_args.seq_len:
+            raise ValueError(f"PagedKVCache capacity {capacity} exceeds the model's seq_len {model_args.seq_len} "
+                             f"(the extent of the RoPE table)")
+        if batch < 1 or capacity < 1:
+            raise ValueError(f"PagedKVCache needs batch >= 1 and capacity >= 1, got {batch}, {capacity}")
+        self.batch, self.capacity, self.dtype, self.page_size = batch, capacity, dtype, page_size
+        self.pages_per_seq = -(-capacity // page_size)
+        self.n_pages = batch * self.pages_per_seq if n_pages is None else int(n_pages)
+        if self.n_pages < 1:
+            raise ValueError(f"PagedKVCache needs n_pages >= 1, got {n_pages}")
+        shape = (model_args.n_layers, self.n_pages, page_size, model_args.kv_heads, model_args.head_dim)
+        self._k = torch.zeros(shape, dtype=dtype, device=device)
+        self._v = torch.zeros_like(self._k)
+        self.k = list(self._k.unbind(0))
+        self.v = list(self._v.unbind(0))
+        self.k_scale, self.v_scale = [None] * model_args.n_layers, [None] * model_args.n_layers
+        self.kv_len = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.block_table = torch.full((batch, self.pages_per_seq), -1, dtype=torch.int32, device=device)
+        self._free = list(range(self.n_pages - 1, -1, -1))  # pop() hands out ascending ids
+        self._refs = [0] * self.n_pages
+        self._pages: List[List[int]] = [[] for _ in range(batch)]  # the mapped prefix of each table row
+
+    def _push(self, b: int) -> None:
+        row = self._pages[b] + [-1] * (self.pages_per_seq - len(self._pages[b]))
+        self.block_table[b].copy_(torch.tensor(row, dtype=torch.int32))
+
+    def _take(self, n: int, what: str) -> List[int]:
+        if n > len(self._free):
+            raise RuntimeError(f"PagedKVCache: {what} needs {n} more page(s) of {self.page_size} tokens, the pool of "
+                               f"{self.n_pages} has {len(self._free)} free: short by {n - len(self._free)}")
+        got = [self._free.pop() for _ in range(n)]
+        for p in got:
+            self._refs[p] = 1
+        return got
+
+    def reserve(self, b: int, n_tokens: int) -> None:
+        """Map pages so that sequence ``b`` can hold ``n_tokens`` (<= capacity). Idempotent, grows only."""
+        if not 0 <= n_tokens <= self.capacity:
+            raise ValueError(f"PagedKVCache.reserve: n_tokens must be in 0 .. {self.capacity}, got {n_tokens}")
+        more = -(-n_tokens // self.page_size) - len(self._pages[b])
+        if more <= 0:
+            return
+        self._pages[b] += self._take(more, f"reserve({b}, {n_tokens})")
+        self._push(b)
+
+    def release(self, b: int) -> None:
+        """Unmap sequence ``b`` (``kv_len[b]`` = 0); pages nobody else names go back to the free list."""
+        for p in self._pages[b]:
+            self._refs[p] -= 1
+            if self._refs[p] == 0:
+                self._free.append(p)
+        self._pages[b] = []
+        self._push(b)
+        self.kv_len[b] = 0
+
+    def share_prefix(self, src: int, dst: int, n_tokens: int) -> None:
+        """Sequence ``dst`` (released first) becomes a copy of the first ``n_tokens`` (a host int, at most what
+        ``src`` holds) of ``src``: it names ``src``'s first ``n_tokens // page_size`` pages, gets a fresh page with a
+        device copy of the partial page if there is one, and ``kv_len[dst] = n_tokens``. Whatever ``dst`` appends
+        from there on lands on pages it owns alone."""
+        full, rem = divmod(int(n_tokens), self.page_size)
+        if src == dst or n_tokens < 0 or full + (rem > 0) > len(self._pages[src]):
+            raise ValueError(f"PagedKVCache.share_prefix: sequence {src} has no {n_tokens} tokens mapped to share "
+                             f"with {dst}")
+        self.release(dst)
+        own = self._take(1, f"share_prefix({src}, {dst}, {n_tokens})") if rem else []
+        shared = self._pages[src][:full]
+        for p in shared:
+            self._refs[p] += 1
+        if rem:
+            s = self._pages[src][full]
+            self._k[:, own[0], :rem].copy_(self._k[:, s, :rem])
+            self._v[:, own[0], :rem].copy_(self._v[:, s, :rem])
+        self._pages[dst] = shared + own
+        self._push(dst)
+        self.kv_len[dst] = int(n_tokens)
+
+    def pages_in_use(self) -> int:
+        return self.n_pages - len(self._free)
+
+    def nbytes(self) -> int:
+        """Bytes of the pools and the table (what the cache allocates, whatever is mapped)."""
+        return 2 * self._k.numel() * self._k.element_size() + self.block_table.numel() * 4
+
+
+def _paged_kw(cache) -> Dict:
+    """The keyword arguments that make the cache ops below walk pages: none for a dense cache."""
+    if isinstance(cache, PagedKVCache):
+        return {"block_table": cache.block_table, "cap": cache.capacity}
+    return {}
+
+
 def _decode_hip(qkv: torch.Tensor, head_dim: int) -> bool:
     return F._note_fallback("decode attention", qkv, _ext.hip16(qkv) and head_dim in (64, 128))
 
 
-def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None) -> None:
+def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None, block_table=None, cap=None) -> None:
     """The new tokens' fused QKV rows [B * T, (Hq + 2 Hkv) D], T per sequence (B is the caches'): row
     b * T + t has q rotated in place at position kv_len[b] + t, rotated k and plain v into that cache row.
     Bit-equal to ``rope_`` on the same row at that position. T = 1 clamps the row to cap - 1; with T > 1 a
     position at or beyond the capacity stores nothing (its q takes table row cap - 1).
     With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows, for any T, are quantized on
-    the way in -- the cache is a pure function of what the 16-bit cache would hold."""
+    the way in -- the cache is a pure function of what the 16-bit cache would hold.
+    With ``block_table`` (and the logical capacity ``cap``) the caches are the pools of a :class:`PagedKVCache`: the
+    same rows through the table, bit for bit; a token whose page is unmapped stores nothing."""
     fp8 = k_scale is not None
-    if _decode_hip(qkv, k_cache.shape[-1]):
+    if block_table is not None:
+        if _decode_hip(qkv, k_cache.shape[-1]):
+            _ext.require_for(qkv).rope_append_paged_(qkv, tab, kv_len, k_cache, v_cache, block_table, cap)
+        else:
+            ref.rope_append_paged_ref(qkv, tab, kv_len, k_cache, v_cache, block_table, cap)
+    elif _decode_hip(qkv, k_cache.shape[-1]):
         C = _ext.require_for(qkv)
         if fp8:
             C.rope_append_fp8_(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
@@ -120,12 +251,20 @@ def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None) 
 
 
 def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None, k_scale=None,
-                     v_scale=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     v_scale=None, block_table=None, cap=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, Hq, D] over the caches [B, cap, Hkv, D]: sequence b attends to keys 0 .. kv_len[b] - 1.
     Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path).
-    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8) and the keys are their dequantized rows."""
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8) and the keys are their dequantized rows.
+    With ``block_table`` / ``cap`` they are the pools of a :class:`PagedKVCache`: ``attn_decode_paged``, bit-equal
+    to the dense kernel on the gathered cache."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     fp8 = k_scale is not None
+    if block_table is not None:
+        if _decode_hip(q, q.shape[-1]):
+            o, lse = _ext.require_for(q).attn_decode_paged(q, k_cache, v_cache, block_table, kv_len, cap, scale)
+            return o, lse
+        o, lse = ref.attention_decode_paged_ref(q, k_cache, v_cache, block_table, kv_len, cap, scale)
+        return o.to(q.dtype), lse
     if _decode_hip(q, q.shape[-1]):
         C = _ext.require_for(q)
         if fp8:
@@ -141,7 +280,7 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
 
 
 def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None, split: Optional[bool] = None,
-                     k_scale=None, v_scale=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     k_scale=None, v_scale=None, block_table=None, cap=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, T, Hq, D] over the caches [B, cap, Hkv, D], which hold the T new tokens' k / v already
     (:func:`rope_append` first); ``kv_len`` [B] counts the tokens held before the append. Query t of
     sequence b attends to keys 0 .. min(kv_len[b] + t, cap - 1). Returns (o [B, T, Hq, D] in q's dtype,
@@ -158,9 +297,20 @@ def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8, the new rows quantized by :func:`rope_append`) and
     the keys are their dequantized rows, a query's own row and the other new rows included:
     csrc/kernels/attention_extend_fp8.hip, which converts the bytes once while staging them and is the 16-bit
-    kernel from there on. Same ``split``, same plan, same contract."""
+    kernel from there on. Same ``split``, same plan, same contract.
+
+    With ``block_table`` / ``cap`` the caches are the pools of a :class:`PagedKVCache`: ``attn_extend_paged``, both
+    arms, the same plan (it does not depend on paging), bit-equal to the dense kernel at the same ``split`` on the
+    gathered cache."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     fp8 = k_scale is not None
+    if block_table is not None:
+        if _decode_hip(q, q.shape[-1]):
+            sp = -1 if split is None else int(bool(split))
+            o, lse = _ext.require_for(q).attn_extend_paged(q, k_cache, v_cache, block_table, kv_len, cap, scale, sp)
+            return o, lse
+        o, lse = ref.attention_extend_paged_ref(q, k_cache, v_cache, block_table, kv_len, cap, scale)
+        return o.to(q.dtype), lse
     if _decode_hip(q, q.shape[-1]):
         C, sp = _ext.require_for(q), -1 if split is None else int(bool(split))
         if fp8:
@@ -175,10 +325,16 @@ def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     return o.to(q.dtype), lse
 
 
-def _store_prompt_kv(k, v, kc, vc, ks, vs) -> None:
-    """The k / v views [B, S, Hkv, D] of the fused QKV activation into cache rows 0 .. S - 1."""
+def _store_prompt_kv(k, v, kc, vc, ks, vs, block_table=None, cap=None) -> None:
+    """The k / v views [B, S, Hkv, D] of the fused QKV activation into cache rows 0 .. S - 1 (with ``block_table``:
+    logical rows of a paged cache; prompt padding beyond a sequence's mapped pages goes nowhere)."""
     S = k.shape[1]
-    if ks is None:
+    if block_table is not None:
+        if _decode_hip(k, k.shape[-1]):
+            _ext.require_for(k).kv_store_paged_(k, v, kc, vc, block_table, cap)
+        else:
+            ref.kv_store_paged_ref(k, v, kc, vc, block_table, cap)
+    elif ks is None:
         kc[:, :S].copy_(k)  # strided copies
         vc[:, :S].copy_(v)
     elif _decode_hip(k, k.shape[-1]):
@@ -193,7 +349,7 @@ def _qkv_params(at):
     return [at.wq.weight, at.wk.weight, at.wv.weight]
 
 
-def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc, ks=None, vs=None):
+def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc, ks=None, vs=None, **paged):
     """The forward of ops/fused.py ``_AttentionBlock`` (same kernels, same rounding points), which also
     leaves the rotated k and the plain v of positions 0 .. S - 1 in the cache (quantized when the cache is
     fp8; the attention itself runs on the unquantized k and v)."""
@@ -217,7 +373,7 @@ def _prefill_attention(model, layer, n1, B: int, S: int, kc, vc, ks=None, vs=Non
     q = qkv[:, :nq].view(B, S, Hq, D)
     k = qkv[:, nq:nq + nk].view(B, S, Hkv, D)
     v = qkv[:, nq + nk:].view(B, S, Hkv, D)
-    _store_prompt_kv(k, v, kc, vc, ks, vs)
+    _store_prompt_kv(k, v, kc, vc, ks, vs, **paged)
     o, _ = F._attn_fwd(q, k, v, 1.0 / math.sqrt(D), True)
     return F._mm_nt(o.view(T, nq), w_o, "o").view(B, S, -1)
 
@@ -238,8 +394,10 @@ def _head(model, h, pending):
     return torch.nn.functional.linear(nf, model.output.weight)
 
 
-def _check_cache(model, cache: KVCache, B: int):
+def _check_cache(model, cache, B: int):
     a = model.model_args
+    if isinstance(cache, PagedKVCache) and tuple(cache.block_table.shape) != (cache.batch, cache.pages_per_seq):
+        raise ValueError("PagedKVCache: the block table must be [batch, ceil(capacity / page_size)]")
     if cache.batch != B or len(cache.k) != a.n_layers or tuple(cache.k[0].shape[2:]) != (a.kv_heads, a.head_dim):
         raise ValueError("KVCache does not match the model / batch")
     w = model.tok_embeddings.weight
@@ -273,6 +431,7 @@ def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens.contiguous(), emb, model._slot([emb]))
     pending = None
+    paged = _paged_kw(cache)
     for i, layer in enumerate(model.layers.values()):
         if pending is None:
             x, n1 = h, model._norm(layer.attention_norm, h, None)
@@ -281,9 +440,9 @@ def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
         at = layer.attention
         qkv = torch.mm(n1.reshape(B * T, n1.shape[-1]), model._weight(_qkv_params(at)).t())
         ks, vs = cache.k_scale[i], cache.v_scale[i]  # None for a cache in the model's dtype
-        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs)
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs, **paged)
         o, _ = attention_extend(qkv[:, :nq].view(B, T, Hq, D), cache.k[i], cache.v[i], cache.kv_len, scale,
-                                k_scale=ks, v_scale=vs)
+                                k_scale=ks, v_scale=vs, **paged)
         att = F._mm_nt(o.view(B * T, nq), model._weight([at.wo.weight]), "o").view(B, T, -1)
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
@@ -378,12 +537,14 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens, emb, model._slot([emb]))
     pending = None
+    paged = _paged_kw(cache)
     for i, layer in enumerate(model.layers.values()):
         if pending is None:
             x, n1 = h, model._norm(layer.attention_norm, h, None)
         else:
             x, n1 = model._norm(layer.attention_norm, h, pending)
-        att = _prefill_attention(model, layer, n1, B, S, cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i])
+        att = _prefill_attention(model, layer, n1, B, S, cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i],
+                                 **paged)
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
     cache.kv_len.copy_(lens.clamp(0, cache.capacity))
@@ -407,6 +568,7 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens.reshape(B, 1), emb, model._slot([emb])).view(B, -1)
     pending = None
+    paged = _paged_kw(cache)
     for i, layer in enumerate(model.layers.values()):
         if pending is None:
             x, n1 = h, model._norm(layer.attention_norm, h, None)
@@ -415,8 +577,8 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
         at = layer.attention
         qkv = torch.mm(n1, model._weight(_qkv_params(at)).t())
         ks, vs = cache.k_scale[i], cache.v_scale[i]  # None: a cache in the model's dtype
-        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs)
-        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale, ks, vs)
+        rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs, **paged)
+        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale, ks, vs, **paged)
         att = F._mm_nt(o.view(B, nq), model._weight([at.wo.weight]), "o")
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
@@ -583,8 +745,8 @@ def _graph_refusal(model, device, dtype, sampler: str, temperature: float, use_c
 def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
              stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
-             kv_cache_dtype: str = "model", prefill_chunk: int = 0,
-             fp8_extend: bool = False) -> Tuple[List[List[int]], List[str]]:
+             kv_cache_dtype: str = "model", prefill_chunk: int = 0, fp8_extend: bool = False,
+             kv_page_size: int = 0) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -615,7 +777,15 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     order. It needs the cache and refuses ``kv_cache_dtype="fp8"`` unless ``fp8_extend=True``: then every piece
     attends to dequantized cache rows (:func:`extend`), and the tokens differ from the one-shot prefill's by
     quantization error too. The flag does nothing for a ``"model"`` cache. ``stats["prefill_chunks"]`` is the
-    number of pieces (0: the one-shot prefill)."""
+    number of pieces (0: the one-shot prefill).
+
+    ``kv_page_size=N`` (64, 128 or 256; 0, the default, is the dense cache exactly as before) keeps the cache in
+    pages of N tokens (:class:`PagedKVCache`, csrc/kernels/attention_paged.hip) with the same logical capacity:
+    sequence b gets ``ceil(min(cap, len_b + max_new_tokens) / N)`` pages, reserved before the prefill, instead of
+    the longest sequence's rows, so a ragged batch pays for what it can use. The tokens are the dense cache's
+    (the paged kernels return its bits) and the table is static while decoding, so ``graph=True`` works. It needs
+    ``use_cache=True`` and ``kv_cache_dtype="model"``. ``stats["kv_cache_bytes"]`` is the cache's allocation, for
+    both layouts (0 without a cache)."""
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
     if sampler not in ("torch", "philox"):
@@ -624,6 +794,11 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         raise ValueError(f"generate: kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
     if kv_cache_dtype != "model" and not use_cache:
         raise ValueError(f"generate: kv_cache_dtype={kv_cache_dtype!r} needs the KV cache (use_cache=True)")
+    if kv_page_size != 0 and kv_page_size not in PAGE_SIZES:
+        raise ValueError(f"generate: kv_page_size must be 0 (the dense cache) or one of {PAGE_SIZES}, got {kv_page_size}")
+    if kv_page_size and (not use_cache or kv_cache_dtype != "model"):
+        raise ValueError("generate: kv_page_size needs the KV cache (use_cache=True) in the model's dtype "
+                         "(kv_cache_dtype='model'): a paged fp8 cache is a follow-up")
     if prefill_chunk < 0 or (prefill_chunk > 0 and not use_cache):
         raise ValueError("generate: prefill_chunk must be >= 0 and needs the KV cache (use_cache=True)")
     device, dtype = _model_device_dtype(model)
@@ -655,8 +830,15 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
 
     timer = _Timer(device)
     timer.mark()
-    if use_cache:
+    cache = None
+    if use_cache and kv_page_size:
+        need = [min(cap, n + max_new_tokens) for n in lens_host]  # tokens a sequence can ever hold
+        cache = PagedKVCache(args, B, cap, dtype, device, kv_page_size, sum(-(-n // kv_page_size) for n in need))
+        for b, n in enumerate(need):
+            cache.reserve(b, n)
+    elif use_cache:
         cache = KVCache(args, B, cap, dtype, device, kv_cache_dtype)
+    if use_cache:
         logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk, fp8_extend=fp8_extend)
     else:
         bi = torch.arange(B, device=device)
@@ -717,6 +899,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         stats["decode_ms_per_token"] = t[1] / steps if steps else 0.0
         stats["decode_steps"] = steps
         stats["prefill_chunks"] = -(-S // prefill_chunk) if prefill_chunk > 0 else 0
+        stats["kv_cache_bytes"] = cache.nbytes() if cache is not None else 0
         stats["graph_replays"] = max(0, dgraph.steps - DecodeGraph.WARMUP) if graph else 0
 
     out_h, count_h = out.cpu(), count.cpu().tolist()

@@ -292,6 +292,62 @@ def _rope_new_rows(qkv, tab, kv_len, B: int, cap: int, Hkv: int, D: int):
 
 
 # ---------------------------------------------------------------------------------------
+# Paged KV cache (HIP: csrc/kernels/attention_paged.hip). pool [n_pages, page, Hkv, D]; block_table integer
+# [B, ceil(cap / page)]: logical key j of sequence b is row j % page of page block_table[b, j // page]. An entry
+# < 0 or >= n_pages is unmapped. The refs are the dense refs on the gathered cache; they define the result
+# wherever every page below a sequence's bound is mapped, which is all the allocator ever exposes.
+
+def _paged_rows(pool, block_table, cap: int):
+    """(flat pool row [B, cap] of every logical key, clamped to 0 where unmapped; mapped [B, cap])."""
+    n_pages, page = pool.shape[0], pool.shape[1]
+    bt = block_table.to(device=pool.device, dtype=torch.long)
+    j = torch.arange(cap, device=pool.device)
+    e = bt[:, j // page]  # [B, cap]
+    ok = (e >= 0) & (e < n_pages)
+    return torch.where(ok, e * page + j % page, torch.zeros_like(e)), ok
+
+
+def paged_gather(pool, block_table, cap: int) -> torch.Tensor:
+    """The dense cache [B, cap, Hkv, D] a paged cache stands for, zeros where the page is unmapped."""
+    rows, ok = _paged_rows(pool, block_table, cap)
+    flat = pool.reshape(-1, *pool.shape[2:])
+    return flat[rows].masked_fill(~ok.view(*ok.shape, 1, 1), 0)
+
+
+def attention_decode_paged_ref(q, k_pool, v_pool, block_table, kv_len, cap: int, scale: Optional[float] = None):
+    """:func:`attention_decode_ref` on the gathered cache."""
+    return attention_decode_ref(q, paged_gather(k_pool, block_table, cap), paged_gather(v_pool, block_table, cap),
+                                kv_len, scale)
+
+
+def attention_extend_paged_ref(q, k_pool, v_pool, block_table, kv_len, cap: int, scale: Optional[float] = None):
+    """:func:`attention_extend_ref` on the gathered cache."""
+    return attention_extend_ref(q, paged_gather(k_pool, block_table, cap), paged_gather(v_pool, block_table, cap),
+                                kv_len, scale)
+
+
+def rope_append_paged_ref(qkv, tab, kv_len, k_pool, v_pool, block_table, cap: int) -> None:
+    """:func:`rope_append_ref` with the rows scattered through the table: same rows, same overflow rule; a
+    token whose page is unmapped stores nothing (its q is rotated all the same)."""
+    B = block_table.shape[0]
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, B, cap, k_pool.shape[2], k_pool.shape[3])
+    rows, ok = _paged_rows(k_pool, block_table, cap)
+    keep = ok[bi, pos]
+    dst = rows[bi, pos][keep]
+    k_pool.view(-1, *k_pool.shape[2:])[dst] = k[keep]
+    v_pool.view(-1, *v_pool.shape[2:])[dst] = v[keep]
+
+
+def kv_store_paged_ref(k, v, k_pool, v_pool, block_table, cap: int) -> None:
+    """k, v [B, S, Hkv, D] into logical rows 0 .. S - 1, rows on unmapped pages skipped."""
+    S = k.shape[1]
+    rows, ok = _paged_rows(k_pool, block_table, cap)
+    rows, ok = rows[:, :S], ok[:, :S]
+    k_pool.view(-1, *k_pool.shape[2:])[rows[ok]] = k[ok]
+    v_pool.view(-1, *v_pool.shape[2:])[rows[ok]] = v[ok]
+
+
+# ---------------------------------------------------------------------------------------
 # fp8 KV cache (HIP: csrc/kernels/attention_decode_fp8.hip). A cache row, the D values of one (sequence,
 # position, kv head), is D bytes of OCP e4m3fn (held as uint8) and one fp32 scale 2^e.
 

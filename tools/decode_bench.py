@@ -17,6 +17,7 @@ Every timed call reads another layer's cache (as a decode step does), and the la
     python tools/decode_bench.py --extend 8 --extend-split 0 --shapes llama3-8b   # ... on the single pass (1: the key split)
     python tools/decode_bench.py --extend 2048 --extend-base 0 --shapes 7b --batch 4 --ctx 2048   # ... beside docs_fwd
     python tools/decode_bench.py --prefill 4096 --prefill-chunk 0,512 --shapes 7b --batch 4 --layers 32
+    python tools/decode_bench.py --page-size 64,128,256 [--extend 8]    # the paged kernels beside the dense ones
 
 ``--extend T`` times ``attn_extend`` (csrc/kernels/attention_extend.hip) alone: T new queries per sequence over
 a cache that held ``--extend-base`` keys before (default ctx - T). ``--prefill S`` times ``prefill`` of a B x S
@@ -194,6 +195,57 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model
     return hip
 
 
+def bench_paged(name, cfg, B, ctx, pages, T, base, iters, dev, split=-1):
+    """The paged kernels (csrc/kernels/attention_paged.hip) beside the dense ones on the same logical contents:
+    ``attn_decode_paged`` over ctx keys (T = 0) or ``attn_extend_paged`` with T queries over ``base`` keys. Every
+    page size's pool holds the dense caches' pages in a shuffled order. The arms alternate over three rounds;
+    every round's time is printed, the medians are compared, and the outputs must be bit-equal."""
+    C = _ext.native()
+    Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
+    base = (ctx - T if base is None else base) if T else ctx
+    per_layer = 2 * B * (base + T) * Hkv * D * 2
+    n_buf = max(2, -(-2 * L3_BYTES // per_layer))
+    ks = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    vs = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    q = torch.randn(B, max(T, 1), Hq, D, device=dev).bfloat16()
+    n = torch.full((B,), base, device=dev, dtype=torch.int32)
+    scale = 1 / math.sqrt(D)
+    if T:
+        dense = lambda i: C.attn_extend(q, ks[i % n_buf], vs[i % n_buf], n, scale, split)  # noqa: E731
+    else:
+        dense = lambda i: C.attn_decode(q[:, 0], ks[i % n_buf], vs[i % n_buf], n, scale)  # noqa: E731
+    what = f"attn_extend T={T} over kv_len={base}, split {split}" if T else "attn_decode"
+    print(f"{name}: {what}, B={B} cap={ctx} Hq/Hkv={Hq}/{Hkv} D={D}, {per_layer / 2**20:.0f} MiB of K/V, "
+          f"{n_buf} caches in rotation; dense vs paged, us (three rounds, median)")
+    for page in pages:
+        P = -(-ctx // page)
+        perm = torch.randperm(B * P, generator=torch.Generator().manual_seed(page)).to(dev)
+        bt = torch.empty(B * P, dtype=torch.int32, device=dev)
+        bt[perm] = torch.arange(B * P, dtype=torch.int32, device=dev)  # pool page j holds dense page perm[j]
+        bt = bt.view(B, P)
+
+        def pool(x):
+            pad = torch.zeros(B, P * page, Hkv, D, dtype=x.dtype, device=dev)
+            pad[:, :ctx] = x
+            return pad.view(B * P, page, Hkv, D)[perm].contiguous()
+
+        kps, vps = [pool(k) for k in ks], [pool(v) for v in vs]
+        if T:
+            paged = lambda i: C.attn_extend_paged(q, kps[i % n_buf], vps[i % n_buf], bt, n, ctx, scale, split)  # noqa: E731
+        else:
+            paged = lambda i: C.attn_decode_paged(q[:, 0], kps[i % n_buf], vps[i % n_buf], bt, n, ctx, scale)  # noqa: E731
+        td, tp = [], []
+        for _ in range(3):
+            td.append(timed_us(dense, iters))
+            tp.append(timed_us(paged, iters))
+        same = all(torch.equal(a, b) for a, b in zip(dense(0), paged(0)))
+        md, mp = sorted(td)[1], sorted(tp)[1]
+        print(f"  page {page:3d}: dense {md:8.1f} ({' '.join(f'{x:.1f}' for x in td)})  paged {mp:8.1f} "
+              f"({' '.join(f'{x:.1f}' for x in tp)})  paged / dense {mp / md:.3f}  {per_layer / mp / 1e6:5.2f} TB/s  "
+              f"bit-equal: {same}")
+        del kps, vps
+
+
 def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="model"):
     """``prefill`` of a B x S prompt, one-shot (chunk 0) and in pieces: milliseconds and the peak of
     ``torch.cuda.max_memory_allocated`` above what the model and the cache hold. An fp8 cache takes the pieces
@@ -365,6 +417,9 @@ def main():
                     help="keys the cache held before the append (default: ctx - T; 0 also times docs_fwd beside it)")
     ap.add_argument("--extend-split", choices=("auto", "0", "1"), default="auto",
                     help="--extend: the kernel by plan (auto), the single pass (0) or the key split (1)")
+    ap.add_argument("--page-size", default="", metavar="64,128,256",
+                    help="time the paged kernels against the dense ones on the same contents, pages shuffled: "
+                         "attn_decode_paged, or with --extend T attn_extend_paged")
     ap.add_argument("--prefill", type=int, default=0, metavar="S",
                     help="time prefill of a B x S prompt, once per --prefill-chunk value, with its peak memory")
     ap.add_argument("--prefill-chunk", default="0,512", help="comma list of chunk sizes for --prefill (0: one-shot)")
@@ -377,6 +432,11 @@ def main():
     _ext.native()
     if a.sample_bench:
         bench_sampler(a.iters, dev)
+        return
+    if a.page_size:
+        for name, preset, B, ctx in shapes:
+            bench_paged(name, get_preset(preset), B, ctx, [int(p) for p in a.page_size.split(",")], a.extend,
+                        a.extend_base, a.iters, dev, -1 if a.extend_split == "auto" else int(a.extend_split))
         return
     if a.extend:
         for name, preset, B, ctx in shapes:
