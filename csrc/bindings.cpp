@@ -1351,6 +1351,46 @@ std::vector<at::Tensor> attn_decode_paged(const at::Tensor& q, const at::Tensor&
   return {o, lse};
 }
 
+// attn_decode_paged for B / group_size groups of group_size consecutive sequences whose table rows agree on a
+// prefix of shared_len[g] tokens (int32 [B / group_size] on q's device): the shared pages are read once per group
+// (csrc/kernels/attention_decode_shared.hip). Same result up to fp32 summation order; the same bits when every
+// shared_len is 0.
+std::vector<at::Tensor> attn_decode_shared_paged(const at::Tensor& q, const at::Tensor& k_pool,
+                                                 const at::Tensor& v_pool, const at::Tensor& block_table,
+                                                 const at::Tensor& kv_len, const at::Tensor& shared_len,
+                                                 int64_t group_size, int64_t cap, double scale) {
+  const Range range_("pyrecover::attn_decode_shared_paged");
+  check_dev(q, "q");
+  TORCH_CHECK(q.dim() == 3, "attn_decode_shared_paged: q must be [B, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), Hq = q.size(1), D = q.size(2);
+  check_paged_common(q, k_pool, v_pool, block_table, &kv_len, B, cap, "attn_decode_shared_paged");
+  const int64_t Hkv = k_pool.size(2);
+  TORCH_CHECK(k_pool.size(3) == D, "attn_decode_shared_paged: q and the pools disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0,
+              "attn_decode_shared_paged: n_heads must be a multiple of n_kv_heads");
+  TORCH_CHECK(group_size >= 1, "attn_decode_shared_paged: group_size must be >= 1, got ", group_size);
+  TORCH_CHECK(B % group_size == 0, "attn_decode_shared_paged: group_size ", group_size, " must divide the batch ", B);
+  same_dev(q, shared_len, "shared_len");
+  TORCH_CHECK(shared_len.scalar_type() == at::kInt && shared_len.dim() == 1 && shared_len.size(0) == B / group_size &&
+                  shared_len.is_contiguous(),
+              "attn_decode_shared_paged: shared_len must be contiguous int32 [B / group_size] = [", B / group_size,
+              "], got ", shared_len.scalar_type(), " ", shared_len.sizes());
+  at::Tensor qc = q.contiguous();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_decode_shared_paged: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, Hq}, q.options().dtype(at::kFloat));
+  at::Tensor ws = at::empty({pra_attn_decode_ws_floats((int)B, (int)Hq, (int)D, (int)cap)},
+                            q.options().dtype(at::kFloat));
+  check(pra_attn_decode_shared_paged(dt(q), qc.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                     block_table.data_ptr<int>(), kv_len.data_ptr<int>(), shared_len.data_ptr<int>(),
+                                     o.data_ptr(), lse.data_ptr<float>(), ws.data_ptr<float>(), (int)B, (int)group_size,
+                                     (int)Hq, (int)Hkv, (int)D, (int)cap, (int)k_pool.size(1), (int)k_pool.size(0),
+                                     (float)scale, stream_of(q)),
+        "attn_decode_shared_paged");
+  return {o, lse};
+}
+
 // attn_extend over a paged cache, which holds the T new tokens already -> (o [B, T, Hq, D], lse fp32 [B, T, Hq]).
 // split and the workspace as attn_extend.
 std::vector<at::Tensor> attn_extend_paged(const at::Tensor& q, const at::Tensor& k_pool, const at::Tensor& v_pool,
@@ -1622,6 +1662,9 @@ PYBIND11_MODULE(_C, m) {
         py::arg("block_table"), py::arg("cap"));
   m.def("attn_decode_paged", &attn_decode_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
         py::arg("block_table"), py::arg("kv_len"), py::arg("cap"), py::arg("scale"));
+  m.def("attn_decode_shared_paged", &attn_decode_shared_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
+        py::arg("block_table"), py::arg("kv_len"), py::arg("shared_len"), py::arg("group_size"), py::arg("cap"),
+        py::arg("scale"));
   m.def("attn_extend_paged", &attn_extend_paged, py::arg("q"), py::arg("k_pool"), py::arg("v_pool"),
         py::arg("block_table"), py::arg("kv_len"), py::arg("cap"), py::arg("scale"), py::arg("split") = -1);
   m.def("sample_", &sample_, py::arg("logits"), py::arg("tok"), py::arg("temperature"), py::arg("top_k"),

@@ -33,11 +33,15 @@
 //
 // Compiled with the flags of attention_extend_split.hip (-fno-honor-nans: no NaN is formed).
 // The tile loop now exists five times and is kept in step by hand: attention_extend.hip,
-// attention_extend_split.hip, attention_extend_fp8.hip (both arms) and the two extend kernels here; the decode
-// chunk kernel is a second copy of attention_decode.hip's, rope_append_paged_kernel of its rope_append_kernel.
+// attention_extend_split.hip, attention_extend_fp8.hip (both arms) and the two extend kernels here, and a sixth
+// time, without masks, in attention_decode_shared.hip; the decode chunk kernel is a second copy of
+// attention_decode.hip's, rope_append_paged_kernel of its rope_append_kernel.
+// attention_decode_shared.hip (shared-prefix decode) launches the decode chunk kernel's SH = true instantiation
+// through decode_chunks as its per-sequence remainder; what the files share is in attn_paged.h.
 #include "attn_common.h"
 #include "common.h"
 #include "attn_launch.h"
+#include "attn_paged.h"
 
 #include <math.h>
 
@@ -46,28 +50,8 @@ namespace paged {
 
 using namespace pra::attn;
 
-constexpr int kKC = 256;  // attention_decode.hip's chunk (pra_attn_decode_chunk; checked by the launcher)
 constexpr int kDecWaves = 8;
 constexpr int kDecThreads = 64 * kDecWaves;
-constexpr float kNoMax = -1e30f;  // "no score yet" running max, as in the dense kernels
-
-// c ? x : y on values, as mask arithmetic: a ?: over table entries invites the compiler to select between their
-// addresses and load afterwards, which parks the entries in scratch memory
-__device__ __forceinline__ int sel(bool c, int x, int y) {
-  const int m = -(int)c;
-  return (x & m) | (y & ~m);
-}
-
-// entry i of a small workgroup-uniform array, i uniform: a chain of scalar selects, no indexed register file
-template <int N>
-__device__ __forceinline__ int pick(const int (&e)[N], int i) {
-  int r = e[0];
-#pragma unroll
-  for (int k = 1; k < N; ++k) r = sel(i == k, e[k], r);
-  return r;
-}
-
-__device__ __forceinline__ bool mapped(int e, int n_pages) { return (unsigned)e < (unsigned)n_pages; }
 
 // attention_decode.hip's helpers, same expressions (the bits must match)
 __device__ __forceinline__ void rot_pair(float a, float b, float c, float s, float& o0, float& o1) {
@@ -183,11 +167,14 @@ __global__ __launch_bounds__(256) void kv_store_paged_kernel(const uint4* __rest
 // ---- decode -----------------------------------------------------------------------------
 // attn_decode_chunk_kernel over the pool. grid (NC, Hkv * (G / GT), B); partials as there: ws_o
 // [B][Hq][NC][D] fp32 (unnormalised), ws_ml [B][Hq][NC][2] = (max in log2 units, sum).
-template <typename T, int D, int GT>
+// SH: the per-sequence remainder of the shared-prefix decode (attention_decode_shared.hip). A chunk below the
+// effective shared length of b's group belongs to decode_shared_chunk_kernel: the workgroup leaves at once and
+// writes nothing. Nothing else differs, and without SH the two extra arguments are not read.
+template <typename T, int D, int GT, bool SH>
 __global__ __launch_bounds__(kDecThreads) void attn_decode_chunk_paged_kernel(
     const T* __restrict__ q, const T* __restrict__ kp, const T* __restrict__ vp, const int* __restrict__ bt,
     const int* __restrict__ kv_len, float* __restrict__ ws_o, float* __restrict__ ws_ml, int Hq, int Hkv, int cap,
-    int NC, int ps, int P, int n_pages, float scale_log2) {
+    int NC, int ps, int P, int n_pages, float scale_log2, const int* __restrict__ shared_len, int gsz) {
   constexpr int LPK = D / 8;
   constexpr int KPW = 64 / LPK;
   constexpr int KPB = kDecWaves * KPW;
@@ -202,8 +189,11 @@ __global__ __launch_bounds__(kDecThreads) void attn_decode_chunk_paged_kernel(
   const int hkv = blockIdx.y / tiles;
   const int h0 = hkv * G + (blockIdx.y - hkv * tiles) * GT;  // first query head served here
   const int chunk = blockIdx.x;
-  const int len = min(max(kv_len[b], 0), cap);
   const int c0 = chunk * kKC;
+  if constexpr (SH) {  // workgroup-uniform; its loads need no kv_len[b], so the exit costs no further latency
+    if (shared_prefix_covers(shared_len, kv_len, b / gsz, gsz, cap, c0)) return;
+  }
+  const int len = min(max(kv_len[b], 0), cap);
   if (c0 >= len) return;  // wave-uniform: no table entry, nothing of the pool read, nothing written
 
   // the chunk's table entries (c0 is a multiple of the page): uniform addresses, scalar loads
@@ -714,13 +704,35 @@ __global__ __launch_bounds__(256, 2) void extend_split_paged_kernel(const T* __r
 using WaveSplit = One<1, 2, 4>;
 using GroupTile = One<1, 2, 4, 8>;
 
-// log2(page) for the page sizes served, -1 otherwise
-inline int page_shift(int page) { return page == 64 ? 6 : page == 128 ? 7 : page == 256 ? 8 : -1; }
-
-// what every launcher checks of the pool and the table; P = ceil(cap / page)
-inline bool pool_ok(const void* kp, const void* vp, const int* bt, int cap, int page, int n_pages) {
-  return kp != nullptr && vp != nullptr && bt != nullptr && cap > 0 && page_shift(page) >= 0 && n_pages >= 1 &&
-         (long)n_pages * page <= 0x7fffffffL;
+// Declared in attn_paged.h and also called from attention_decode_shared.hip (its remainder launch): the one
+// function of this file that another translation unit links against besides the extern "C" launchers.
+hipError_t decode_chunks(int dtype, const void* q, const void* k_pool, const void* v_pool, const int* block_table,
+                         const int* kv_len, const int* shared_len, int group_size, float* ws_o, float* ws_ml, int B,
+                         int Hq, int Hkv, int D, int cap, int page, int n_pages, float scale, hipStream_t s) {
+  const int ps = page_shift(page), P = (cap + page - 1) / page;
+  const int NC = (cap + kKC - 1) / kKC;
+  const int G = Hq / Hkv;
+  // the widest head tile that divides the group, as the dense launcher picks it
+  const int GT = G % 8 == 0 ? 8 : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
+  const dim3 grid(NC, Hkv * (G / GT), B);
+  const float sl2 = scale * 1.4426950408889634f;
+  PRA_DISPATCH_16BIT(dtype, T, {
+    const bool found = pra::dispatch(
+        [&](auto d, auto g) {
+          auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(kDecThreads), 0, s, (const T*)q, (const T*)k_pool, (const T*)v_pool,
+                               block_table, kv_len, ws_o, ws_ml, Hq, Hkv, cap, NC, ps, P, n_pages, sl2, shared_len,
+                               group_size);
+          };
+          if (shared_len == nullptr)
+            launch(attn_decode_chunk_paged_kernel<T, d(), g(), false>);
+          else
+            launch(attn_decode_chunk_paged_kernel<T, d(), g(), true>);
+        },
+        HeadDim{D}, GroupTile{GT});
+    if (!found) return hipErrorInvalidValue;
+  });
+  return hipGetLastError();
 }
 
 }  // namespace paged
@@ -776,26 +788,11 @@ hipError_t pra_attn_decode_paged(int dtype, const void* q, const void* k_pool, c
   if (B <= 0 || Hkv <= 0 || Hq <= 0 || Hq % Hkv || B > 65535 || Hq > 65535 || (D != 64 && D != 128) ||
       pra_attn_decode_chunk() != kKC)
     return hipErrorInvalidValue;
-  const int ps = page_shift(page), P = (cap + page - 1) / page;
   const int NC = (cap + kKC - 1) / kKC;
   float* ws_o = ws;
   float* ws_ml = ws + (long)B * Hq * NC * D;
-  const int G = Hq / Hkv;
-  // the widest head tile that divides the group, as the dense launcher picks it
-  const int GT = G % 8 == 0 ? 8 : G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1;
-  const dim3 grid(NC, Hkv * (G / GT), B);
-  const float sl2 = scale * 1.4426950408889634f;
-  PRA_DISPATCH_16BIT(dtype, T, {
-    const bool found = pra::dispatch(
-        [&](auto d, auto g) {
-          hipLaunchKernelGGL((attn_decode_chunk_paged_kernel<T, d(), g()>), grid, dim3(kDecThreads), 0, s, (const T*)q,
-                             (const T*)k_pool, (const T*)v_pool, block_table, kv_len, ws_o, ws_ml, Hq, Hkv, cap, NC, ps,
-                             P, n_pages, sl2);
-        },
-        HeadDim{D}, GroupTile{GT});
-    if (!found) return hipErrorInvalidValue;
-  });
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = decode_chunks(dtype, q, k_pool, v_pool, block_table, kv_len, nullptr, 1, ws_o, ws_ml, B, Hq, Hkv,
+                                     D, cap, page, n_pages, scale, s);
   if (e != hipSuccess) return e;
   return pra_attn_decode_combine(dtype, ws_o, ws_ml, kv_len, o, lse, B, Hq, D, cap, NC, s);
 }

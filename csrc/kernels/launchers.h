@@ -239,6 +239,15 @@ hipError_t pra_attn_extend_paged(int dtype, const void* q, long ldq, const void*
                                  const int* block_table, const int* kv_len, void* o, float* lse, float* ws, int B, int T,
                                  int Hq, int Hkv, int D, int cap, int page, int n_pages, float scale, int split,
                                  hipStream_t s);
+// Shared-prefix decode (attention_decode_shared.hip): pra_attn_decode_paged for a batch of B / group_size groups
+// of group_size consecutive sequences. shared_len int32 [B / group_size] on the device: the leading tokens of
+// group g whose table entries are the same in every member's row. Those keys, in whole chunks and as far as
+// every member attends to them, are read once per group; the rest runs per sequence. Same workspace; nothing is
+// read on the host. With every shared_len 0 the result is pra_attn_decode_paged's, bit for bit.
+hipError_t pra_attn_decode_shared_paged(int dtype, const void* q, const void* k_pool, const void* v_pool,
+                                        const int* block_table, const int* kv_len, const int* shared_len, void* o,
+                                        float* lse, float* ws, int B, int group_size, int Hq, int Hkv, int D, int cap,
+                                        int page, int n_pages, float scale, hipStream_t s);
 
 // fp8 KV cache (attention_decode_fp8.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D] of
 // e4m3fn bytes, k_scale, v_scale fp32 [B][cap][Hkv], powers of two. dtype is the 16-bit type of qkv / q / o.

@@ -66,6 +66,8 @@ EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllv
                                             "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "attention_paged.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
                                        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "attention_decode_shared.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
+                                               "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "attention_extend_split.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
                                               "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 

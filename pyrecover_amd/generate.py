@@ -3,7 +3,7 @@
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
         --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
         [--sampler philox --decode-graph] [--kv-cache-dtype fp8] [--prefill-chunk 512] [--fp8-extend] \
-        [--kv-page-size 128]
+        [--kv-page-size 128 [--n-samples 8]]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
 ``--model-dtype``, ``--tokenizer-name-or-path``) and the checkpoint flags (``--checkpoint-dir``,
@@ -90,6 +90,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="keep the KV cache in pages of N tokens (64, 128 or 256; csrc/kernels/attention_paged.hip): "
                         "every sequence gets the pages its own prompt and --max-new-tokens need, not the longest "
                         "sequence's rows; same tokens. 0 (default): the dense cache. Needs --kv-cache-dtype model")
+    p.add_argument("--n-samples", type=int, default=1, metavar="N",
+                   help="N samples per prompt (records are prompt-major): the prompt is prefilled once, its pages are "
+                        "shared by the N samples, and a decode step reads them once per prompt "
+                        "(csrc/kernels/attention_decode_shared.hip). Needs --kv-page-size; with --sampler philox the "
+                        "samples differ, greedy ones are identical")
     p.add_argument("--no-kv-cache", action="store_true",
                    help="naive path: a full forward over the whole prefix per new token (debugging aid)")
     p.add_argument("--output-jsonl", type=str, default=None,
@@ -125,15 +130,17 @@ def main(argv=None) -> int:
                                top_p=args.top_p, seed=args.seed, eos_id=eos, use_cache=not args.no_kv_cache,
                                stats=stats, sampler=args.sampler, graph=args.decode_graph,
                                kv_cache_dtype=args.kv_cache_dtype, prefill_chunk=args.prefill_chunk,
-                               fp8_extend=args.fp8_extend, kv_page_size=args.kv_page_size)
+                               fp8_extend=args.fp8_extend, kv_page_size=args.kv_page_size,
+                               n_samples=args.n_samples)
     records = []
-    for p, ids, why in zip(prompts, tokens, reasons):
+    for p, ids, why in zip([p for p in prompts for _ in range(args.n_samples)], tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None
         records.append({"prompt_ids": list(p), "generated_ids": ids, "text": text, "finish_reason": why,
                         "prefill_ms": stats["prefill_ms"], "decode_ms_per_token": stats["decode_ms_per_token"],
                         "checkpoint_step": step, "sampler": args.sampler, "decode_graph": args.decode_graph,
                         "kv_cache_dtype": args.kv_cache_dtype, "prefill_chunks": stats["prefill_chunks"],
-                        "kv_page_size": args.kv_page_size, "kv_cache_bytes": stats["kv_cache_bytes"]})
+                        "kv_page_size": args.kv_page_size, "kv_cache_bytes": stats["kv_cache_bytes"],
+                        "n_samples": args.n_samples})
         logger.info(f"[{why}] {ids if text is None else text!r}")
     if args.output_jsonl:
         with open(args.output_jsonl, "w", encoding="utf-8") as f:

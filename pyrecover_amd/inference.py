@@ -116,10 +116,19 @@ class PagedKVCache:
     :meth:`release` / :meth:`share_prefix` push a changed table row with one small host-to-device copy; call
     them outside a captured region and before a decode loop, never inside one (``generate`` reserves every
     sequence's pages before the prefill, so the table is static while decoding). ``n_pages`` defaults to
-    ``batch * ceil(capacity / page_size)``, the dense cache's footprint. A paged fp8 cache is a follow-up."""
+    ``batch * ceil(capacity / page_size)``, the dense cache's footprint. A paged fp8 cache is a follow-up.
+
+    :meth:`fork` turns every sequence into ``group_size`` consecutive rows that share its pages. A forked cache
+    carries ``shared_len`` (int32 [batch / group_size] on the device, with a host mirror): the leading tokens of a
+    group whose table entries are the same in every member's row. ``decode_step`` hands both to
+    ``attn_decode_shared_paged``, which reads those pages once per group. :meth:`release` and
+    :meth:`share_prefix` keep it truthful (they only ever lower it); :meth:`reserve` maps pages after a row's
+    mapped prefix and cannot break it."""
 
     fp8 = False
     kv_dtype = "model"
+    group_size = 1      # > 1 after fork(): rows g * group_size .. (g + 1) * group_size - 1 form group g
+    shared_len = None   # forked: int32 [batch / group_size] on the device
 
     def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device,
                  page_size: int = 128, n_pages: Optional[int] = None, kv_dtype: str = "model"):
@@ -181,17 +190,28 @@ class PagedKVCache:
         self._pages[b] = []
         self._push(b)
         self.kv_len[b] = 0
+        self._set_shared(b // self.group_size, 0)  # its row agrees with nobody's any more
+
+    def _set_shared(self, g: int, n_tokens: int) -> None:
+        if self.group_size > 1 and n_tokens != self._shared[g]:
+            self._shared[g] = n_tokens
+            self.shared_len[g] = n_tokens
 
     def share_prefix(self, src: int, dst: int, n_tokens: int) -> None:
         """Sequence ``dst`` (released first) becomes a copy of the first ``n_tokens`` (a host int, at most what
         ``src`` holds) of ``src``: it names ``src``'s first ``n_tokens // page_size`` pages, gets a fresh page with a
         device copy of the partial page if there is one, and ``kv_len[dst] = n_tokens``. Whatever ``dst`` appends
-        from there on lands on pages it owns alone."""
+        from there on lands on pages it owns alone. On a forked cache ``dst``'s group keeps the part of its
+        ``shared_len`` that the new row still agrees with when ``src`` is a member of it, and none otherwise."""
         full, rem = divmod(int(n_tokens), self.page_size)
         if src == dst or n_tokens < 0 or full + (rem > 0) > len(self._pages[src]):
             raise ValueError(f"PagedKVCache.share_prefix: sequence {src} has no {n_tokens} tokens mapped to share "
                              f"with {dst}")
-        self.release(dst)
+        g = dst // self.group_size
+        keep = 0
+        if self.group_size > 1 and src // self.group_size == g:  # the others agree with src on _shared[g] tokens
+            keep = min(self._shared[g], full * self.page_size)
+        self.release(dst)  # shared_len[g] = 0 until the new row stands
         own = self._take(1, f"share_prefix({src}, {dst}, {n_tokens})") if rem else []
         shared = self._pages[src][:full]
         for p in shared:
@@ -203,6 +223,45 @@ class PagedKVCache:
         self._pages[dst] = shared + own
         self._push(dst)
         self.kv_len[dst] = int(n_tokens)
+        self._set_shared(g, keep)
+
+    def fork(self, n: int, kv_len: Optional[Sequence[int]] = None) -> "PagedKVCache":
+        """A cache of batch ``batch * n`` over the same pools and allocator state, for n samples per sequence; this
+        object must not be used afterwards. New row ``g * n`` takes over old row g's pages; rows ``g * n + 1 ..
+        g * n + n - 1`` are :meth:`share_prefix` copies of it at its current length: the full pages are named
+        again, a partial page is copied into a fresh page per copy. ``group_size = n`` and ``shared_len[g] =
+        (kv_len_g // page_size) * page_size``. ``kv_len``: the host's knowledge of the lengths (``generate`` passes
+        the prompt lengths); without it ``self.kv_len`` is read back once. A pool without ``(n - 1)`` free pages
+        for every partial page raises the allocator's "short by" error and changes nothing."""
+        if n < 1 or self.group_size != 1:
+            raise ValueError(f"PagedKVCache.fork: n must be >= 1 on a cache that is not forked yet, got {n}")
+        lens = [int(x) for x in (self.kv_len.tolist() if kv_len is None else kv_len)]
+        ps, B = self.page_size, self.batch
+        if len(lens) != B or any(L < 0 or -(-L // ps) > len(self._pages[b]) for b, L in enumerate(lens)):
+            raise ValueError(f"PagedKVCache.fork: kv_len must hold {B} lengths inside the mapped pages, got {lens}")
+        own = self._take((n - 1) * sum(L % ps > 0 for L in lens), f"fork({n})")
+        new = object.__new__(PagedKVCache)
+        new.__dict__.update(self.__dict__)  # the pools, the free list and the reference counts are shared
+        new.batch, new.group_size = B * n, n
+        new._pages, new._shared = [], []
+        for g, L in enumerate(lens):
+            full, rem = divmod(L, ps)
+            src = self._pages[g]
+            new._pages.append(src)
+            for p in src[:full]:
+                self._refs[p] += n - 1
+            mine = [own.pop() for _ in range(n - 1)] if rem else []
+            if mine:  # one broadcast copy of the partial page per pool
+                self._k[:, mine, :rem] = self._k[:, src[full]:src[full] + 1, :rem]
+                self._v[:, mine, :rem] = self._v[:, src[full]:src[full] + 1, :rem]
+            new._pages += [src[:full] + [p] for p in mine] if rem else [src[:full] for _ in range(n - 1)]
+            new._shared.append(full * ps)
+        dev = self.kv_len.device
+        rows = [r + [-1] * (self.pages_per_seq - len(r)) for r in new._pages]
+        new.block_table = torch.tensor(rows, dtype=torch.int32).to(dev)
+        new.kv_len = torch.tensor([L for L in lens for _ in range(n)], dtype=torch.int32).to(dev)
+        new.shared_len = torch.tensor(new._shared, dtype=torch.int32).to(dev)
+        return new
 
     def pages_in_use(self) -> int:
         return self.n_pages - len(self._free)
@@ -216,6 +275,13 @@ def _paged_kw(cache) -> Dict:
     """The keyword arguments that make the cache ops below walk pages: none for a dense cache."""
     if isinstance(cache, PagedKVCache):
         return {"block_table": cache.block_table, "cap": cache.capacity}
+    return {}
+
+
+def _group_kw(cache) -> Dict:
+    """The further keyword arguments of :func:`attention_decode` over a forked :class:`PagedKVCache`."""
+    if getattr(cache, "group_size", 1) > 1:
+        return {"group_size": cache.group_size, "shared_len": cache.shared_len}
     return {}
 
 
@@ -251,19 +317,32 @@ def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None, 
 
 
 def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None, k_scale=None,
-                     v_scale=None, block_table=None, cap=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                     v_scale=None, block_table=None, cap=None, group_size: int = 1,
+                     shared_len=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, Hq, D] over the caches [B, cap, Hkv, D]: sequence b attends to keys 0 .. kv_len[b] - 1.
     Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path).
     With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8) and the keys are their dequantized rows.
     With ``block_table`` / ``cap`` they are the pools of a :class:`PagedKVCache`: ``attn_decode_paged``, bit-equal
-    to the dense kernel on the gathered cache."""
+    to the dense kernel on the gathered cache. With ``group_size`` > 1 and ``shared_len`` (int32
+    [B / group_size] on the device; a forked cache's fields) as well, the batch is groups of ``group_size``
+    consecutive sequences whose table rows agree on ``shared_len[g]`` leading tokens: ``attn_decode_shared_paged``
+    (csrc/kernels/attention_decode_shared.hip) reads those pages once per group. The result is the ungrouped one
+    up to fp32 summation order (``ops/reference.py::attention_decode_shared_ref``)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     fp8 = k_scale is not None
+    if group_size != 1 and (block_table is None or shared_len is None):
+        raise ValueError("attention_decode: group_size > 1 needs a paged cache (block_table, cap) and shared_len")
     if block_table is not None:
         if _decode_hip(q, q.shape[-1]):
-            o, lse = _ext.require_for(q).attn_decode_paged(q, k_cache, v_cache, block_table, kv_len, cap, scale)
+            C = _ext.require_for(q)
+            if group_size != 1:
+                o, lse = C.attn_decode_shared_paged(q, k_cache, v_cache, block_table, kv_len, shared_len, group_size,
+                                                    cap, scale)
+            else:
+                o, lse = C.attn_decode_paged(q, k_cache, v_cache, block_table, kv_len, cap, scale)
             return o, lse
-        o, lse = ref.attention_decode_paged_ref(q, k_cache, v_cache, block_table, kv_len, cap, scale)
+        o, lse = ref.attention_decode_shared_ref(q, k_cache, v_cache, block_table, kv_len, cap, scale, group_size,
+                                                 shared_len)
         return o.to(q.dtype), lse
     if _decode_hip(q, q.shape[-1]):
         C = _ext.require_for(q)
@@ -467,7 +546,10 @@ def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, ret
     what ``decode_step`` does for one token: the T new tokens' rotated k and plain v are quantized into the
     cache first, then query t attends to the dequantized cache rows 0 .. min(kv_len[b] + t, cap - 1), its own
     row and the other new rows included. So ``extend`` with T = 1 is ``decode_step``, and with T tokens it
-    equals T ``decode_step`` calls in exact arithmetic. The flag is ignored for a cache in the model's dtype."""
+    equals T ``decode_step`` calls in exact arithmetic. The flag is ignored for a cache in the model's dtype.
+
+    On a forked :class:`PagedKVCache` ``extend`` and the chunked prefill keep using ``attn_extend_paged`` per
+    sequence: only ``decode_step`` reads a group's shared pages once."""
     if tokens.dim() != 2 or tokens.shape[1] < 1:
         raise ValueError(f"extend: tokens must be [B, T] with T >= 1, got {tuple(tokens.shape)}")
     B, T = tokens.shape
@@ -556,7 +638,8 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
 @torch.no_grad()
 def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
     """One token per sequence (tokens [B], the token at position kv_len[b]) -> logits [B, V] for the
-    next position; kv_len grows by one (clamped at the capacity). No host synchronisation."""
+    next position; kv_len grows by one (clamped at the capacity). No host synchronisation. On a forked
+    :class:`PagedKVCache` the attention reads a group's shared pages once (``attn_decode_shared_paged``)."""
     B = tokens.shape[0]
     _check_cache(model, cache, B)
     a = model.model_args
@@ -568,7 +651,7 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens.reshape(B, 1), emb, model._slot([emb])).view(B, -1)
     pending = None
-    paged = _paged_kw(cache)
+    paged, group = _paged_kw(cache), _group_kw(cache)
     for i, layer in enumerate(model.layers.values()):
         if pending is None:
             x, n1 = h, model._norm(layer.attention_norm, h, None)
@@ -578,7 +661,8 @@ def decode_step(model, tokens: torch.Tensor, cache: KVCache) -> torch.Tensor:
         qkv = torch.mm(n1, model._weight(_qkv_params(at)).t())
         ks, vs = cache.k_scale[i], cache.v_scale[i]  # None: a cache in the model's dtype
         rope_append(qkv, model.rope_tab, cache.kv_len, cache.k[i], cache.v[i], ks, vs, **paged)
-        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale, ks, vs, **paged)
+        o, _ = attention_decode(qkv[:, :nq].view(B, Hq, D), cache.k[i], cache.v[i], att_len, scale, ks, vs, **paged,
+                                **group)
         att = F._mm_nt(o.view(B, nq), model._weight([at.wo.weight]), "o")
         h, n2 = model._norm(layer.ffn_norm, x, att)
         pending = _mlp(model, layer, n2)
@@ -746,7 +830,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
              stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
              kv_cache_dtype: str = "model", prefill_chunk: int = 0, fp8_extend: bool = False,
-             kv_page_size: int = 0) -> Tuple[List[List[int]], List[str]]:
+             kv_page_size: int = 0, n_samples: int = 1) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -785,7 +869,18 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     the longest sequence's rows, so a ragged batch pays for what it can use. The tokens are the dense cache's
     (the paged kernels return its bits) and the table is static while decoding, so ``graph=True`` works. It needs
     ``use_cache=True`` and ``kv_cache_dtype="model"``. ``stats["kv_cache_bytes"]`` is the cache's allocation, for
-    both layouts (0 without a cache)."""
+    both layouts (0 without a cache).
+
+    ``n_samples=N`` (N > 1) draws N samples per prompt and returns them prompt-major: index ``p * N + i`` is sample
+    i of prompt p. The B prompts are prefilled once; :meth:`PagedKVCache.fork` then gives every prompt N rows
+    that name its full pages (the pool holds them once, plus each sample's own pages), every sample's first
+    token is drawn from the prompt's logits, and decoding runs on B * N rows whose attention reads a prompt's
+    shared pages once per step (csrc/kernels/attention_decode_shared.hip). ``sampler="philox"`` keys its draws on
+    the row, so the samples of a prompt differ; greedy samples are identical. It needs ``kv_page_size != 0`` and
+    ``use_cache=True``. ``stats["n_samples"]`` records N."""
+    if n_samples < 1 or (n_samples > 1 and not (kv_page_size and use_cache)):
+        raise ValueError("generate: n_samples must be >= 1, and n_samples > 1 needs the paged KV cache "
+                         "(kv_page_size != 0, use_cache=True): the samples of a prompt share its pages")
     if temperature < 0 or not 0.0 < top_p <= 1.0 or top_k < 0 or max_new_tokens < 1:
         raise ValueError("generate: need temperature >= 0, 0 < top_p <= 1, top_k >= 0, max_new_tokens >= 1")
     if sampler not in ("torch", "philox"):
@@ -833,7 +928,10 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     cache = None
     if use_cache and kv_page_size:
         need = [min(cap, n + max_new_tokens) for n in lens_host]  # tokens a sequence can ever hold
-        cache = PagedKVCache(args, B, cap, dtype, device, kv_page_size, sum(-(-n // kv_page_size) for n in need))
+        pages = [-(-n // kv_page_size) for n in need]
+        # a further sample names the prompt's full pages again and owns the rest
+        own = [p - n // kv_page_size for p, n in zip(pages, lens_host)]
+        cache = PagedKVCache(args, B, cap, dtype, device, kv_page_size, sum(pages) + (n_samples - 1) * sum(own))
         for b, n in enumerate(need):
             cache.reserve(b, n)
     elif use_cache:
@@ -843,6 +941,12 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     else:
         bi = torch.arange(B, device=device)
         logits = model(buf[:, :S])[bi, lens - 1]
+    if n_samples > 1:  # from here on B * n_samples rows, prompt-major: the samples of a prompt are one group
+        cache = cache.fork(n_samples, lens_host)
+        for b in range(B * n_samples):
+            cache.reserve(b, need[b // n_samples])
+        B *= n_samples
+        logits, lens, room = (x.repeat_interleave(n_samples, 0) for x in (logits, lens, room))
     timer.mark()
 
     steps = 0
@@ -900,6 +1004,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         stats["decode_steps"] = steps
         stats["prefill_chunks"] = -(-S // prefill_chunk) if prefill_chunk > 0 else 0
         stats["kv_cache_bytes"] = cache.nbytes() if cache is not None else 0
+        stats["n_samples"] = n_samples
         stats["graph_replays"] = max(0, dgraph.steps - DecodeGraph.WARMUP) if graph else 0
 
     out_h, count_h = out.cpu(), count.cpu().tolist()

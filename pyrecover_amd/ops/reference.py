@@ -320,6 +320,15 @@ def attention_decode_paged_ref(q, k_pool, v_pool, block_table, kv_len, cap: int,
                                 kv_len, scale)
 
 
+def attention_decode_shared_ref(q, k_pool, v_pool, block_table, kv_len, cap: int, scale: Optional[float] = None,
+                                group_size: int = 1, shared_len=None):
+    """The contract of ``attn_decode_shared_paged`` (csrc/kernels/attention_decode_shared.hip): the batch is
+    B / group_size groups of consecutive sequences and ``shared_len[g]`` promises that the members' table rows name
+    the same pages for their first ``shared_len[g]`` tokens. The promise only lets the kernel read those pages
+    once; the mathematics do not depend on the grouping, so this is :func:`attention_decode_paged_ref`."""
+    return attention_decode_paged_ref(q, k_pool, v_pool, block_table, kv_len, cap, scale)
+
+
 def attention_extend_paged_ref(q, k_pool, v_pool, block_table, kv_len, cap: int, scale: Optional[float] = None):
     """:func:`attention_extend_ref` on the gathered cache."""
     return attention_extend_ref(q, paged_gather(k_pool, block_table, cap), paged_gather(v_pool, block_table, cap),

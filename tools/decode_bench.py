@@ -246,6 +246,47 @@ def bench_paged(name, cfg, B, ctx, pages, T, base, iters, dev, split=-1):
         del kps, vps
 
 
+def bench_shared(name, cfg, G, ctx, page, N, iters, dev):
+    """``attn_decode_shared_paged`` (csrc/kernels/attention_decode_shared.hip) beside ``attn_decode_paged`` on the same
+    pools and table: G groups of N sequences of ctx keys whose first ctx - page keys are shared pages, the last
+    page each sequence's own, pages shuffled. The arms alternate over three rounds; every round's time is printed
+    and the medians compared. The bytes are those the pools hold (shared pages once) and those the per-sequence
+    kernel streams (shared pages N times)."""
+    C = _ext.native()
+    Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
+    P, B = ctx // page, G * N
+    if ctx % page or P < 2:
+        raise SystemExit(f"--shared: --ctx {ctx} must be at least two whole pages of {page}")
+    npg = G * (P - 1 + N)
+    once, streamed = 2 * npg * page * Hkv * D * 2, 2 * B * ctx * Hkv * D * 2
+    n_buf = max(2, -(-2 * L3_BYTES // once))
+    ids = torch.randperm(npg, generator=torch.Generator().manual_seed(page)).to(torch.int32)
+    bt = torch.empty(G, N, P, dtype=torch.int32)
+    bt[:, :, :P - 1] = ids[:G * (P - 1)].view(G, 1, P - 1)
+    bt[:, :, P - 1] = ids[G * (P - 1):].view(G, N)
+    bt = bt.view(B, P).to(dev)
+    kps = [torch.randn(npg, page, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    vps = [torch.randn(npg, page, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
+    q = torch.randn(B, Hq, D, device=dev).bfloat16()
+    n = torch.full((B,), ctx, device=dev, dtype=torch.int32)
+    sl = torch.full((G,), ctx - page, device=dev, dtype=torch.int32)
+    scale = 1 / math.sqrt(D)
+    each = lambda i: C.attn_decode_paged(q, kps[i % n_buf], vps[i % n_buf], bt, n, ctx, scale)  # noqa: E731
+    shared = lambda i: C.attn_decode_shared_paged(q, kps[i % n_buf], vps[i % n_buf], bt, n, sl, N, ctx, scale)  # noqa: E731
+    te, ts = [], []
+    for _ in range(3):
+        te.append(timed_us(each, iters))
+        ts.append(timed_us(shared, iters))
+    err = max((a.float() - b.float()).abs().max().item() for a, b in zip(each(0), shared(0)))
+    me, ms = sorted(te)[1], sorted(ts)[1]
+    print(f"{name}: attn_decode, {G} groups of {N} x {ctx} keys ({ctx - page} shared), page {page}, Hq/Hkv={Hq}/{Hkv} "
+          f"D={D}; pools {once / 2**20:.0f} MiB, streamed per sequence {streamed / 2**20:.0f} MiB, {n_buf} pools in "
+          f"rotation; us (three rounds, median)")
+    print(f"  per sequence {me:8.1f} ({' '.join(f'{x:.1f}' for x in te)})  {streamed / me / 1e6:5.2f} TB/s streamed   "
+          f"shared {ms:8.1f} ({' '.join(f'{x:.1f}' for x in ts)})  {once / ms / 1e6:5.2f} TB/s of the pools   "
+          f"shared / per sequence {ms / me:.3f}   max |difference| of o, lse {err:.2e}")
+
+
 def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="model"):
     """``prefill`` of a B x S prompt, one-shot (chunk 0) and in pieces: milliseconds and the peak of
     ``torch.cuda.max_memory_allocated`` above what the model and the cache hold. An fp8 cache takes the pieces
@@ -420,6 +461,9 @@ def main():
     ap.add_argument("--page-size", default="", metavar="64,128,256",
                     help="time the paged kernels against the dense ones on the same contents, pages shuffled: "
                          "attn_decode_paged, or with --extend T attn_extend_paged")
+    ap.add_argument("--shared", type=int, default=0, metavar="N",
+                    help="time attn_decode_shared_paged beside attn_decode_paged: the shape's batch as groups of N "
+                         "sequences over a common prefix of --ctx minus one page (--page-size, default 128)")
     ap.add_argument("--prefill", type=int, default=0, metavar="S",
                     help="time prefill of a B x S prompt, once per --prefill-chunk value, with its peak memory")
     ap.add_argument("--prefill-chunk", default="0,512", help="comma list of chunk sizes for --prefill (0: one-shot)")
@@ -432,6 +476,11 @@ def main():
     _ext.native()
     if a.sample_bench:
         bench_sampler(a.iters, dev)
+        return
+    if a.shared:
+        for name, preset, B, ctx in shapes:
+            for page in [int(p) for p in (a.page_size or "128").split(",")]:
+                bench_shared(name, get_preset(preset), B, ctx, page, a.shared, a.iters, dev)
         return
     if a.page_size:
         for name, preset, B, ctx in shapes:
