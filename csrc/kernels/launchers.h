@@ -269,6 +269,20 @@ hipError_t pra_attn_decode_fp8(int dtype, const void* q, const void* k_cache, co
                                float* ws, int B, int Hq, int Hkv, int D, int cap, float scale, hipStream_t s);
 int pra_attn_decode_fp8_chunk();
 
+// MXFP4 KV cache (attention_decode_fp4.hip documents the format): k_cache, v_cache uint8 [B][cap][Hkv][D / 2]
+// of e2m1 nibble pairs, k_scale, v_scale uint8 [B][cap][Hkv][D / 32] of e8m0 exponents, one per block of 32
+// columns. dtype is the 16-bit type of qkv / q / o, D 64 or 128. The three are pra_kv_quantize /
+// pra_rope_append_fp8 / pra_attn_decode_fp8 over this cache: same arguments, rows, overflow rule and workspace.
+hipError_t pra_kv_quantize_fp4(int dtype, const void* k, const void* v, long ld, void* k_cache, void* v_cache,
+                               void* k_scale, void* v_scale, int B, int S, int Hkv, int D, int cap, hipStream_t s);
+hipError_t pra_rope_append_fp4(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,
+                               void* k_scale, void* v_scale, int B, int nt, long ld, int Hq, int Hkv, int D, int cap,
+                               hipStream_t s);
+hipError_t pra_attn_decode_fp4(int dtype, const void* q, const void* k_cache, const void* v_cache, const void* k_scale,
+                               const void* v_scale, const int* kv_len, void* o, float* lse, float* ws, int B, int Hq,
+                               int Hkv, int D, int cap, float scale, hipStream_t s);
+int pra_attn_decode_fp4_chunk();
+
 // Device-side sampling (sample.hip documents the rule), bf16 / fp16 logits [B][ld], ld >= V >= 1, no
 // alignment demand beyond the element. The launcher copies the block before it returns (graph capture).
 // The generation state is optional (done == null: absent). With it the launch also does the bookkeeping

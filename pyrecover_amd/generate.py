@@ -2,7 +2,7 @@
 
     python generate.py --checkpoint-dir checkpoints/ --model-preset llama2-7b --sequence-length 2048 \
         --prompt "Once upon a time" --max-new-tokens 64 --temperature 0.8 --top-p 0.95 --output-jsonl out.jsonl \
-        [--sampler philox --decode-graph] [--kv-cache-dtype fp8] [--prefill-chunk 512] [--fp8-extend] \
+        [--sampler philox --decode-graph] [--kv-cache-dtype fp8|fp4] [--prefill-chunk 512] [--fp8-extend] \
         [--kv-page-size 128 [--n-samples 8]]
 
 The model flags (``--model-preset``, ``--n-layers``, ``--vocab-size``, ``--sequence-length``,
@@ -75,7 +75,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv-cache-dtype", choices=KV_DTYPES, default="model",
                    help="model: the cache holds k / v in the model's dtype. fp8: e4m3fn bytes with one "
                         "power-of-two scale per (token, kv head), about half the cache memory; the prompt's "
-                        "attention stays unquantized, so the first generated token does not change")
+                        "attention stays unquantized, so the first generated token does not change. fp4: OCP "
+                        "MXFP4, e2m1 nibbles with one power-of-two scale per 32 columns "
+                        "(csrc/kernels/attention_decode_fp4.hip), about half the fp8 cache, under the same rule; "
+                        "not with --prefill-chunk or --kv-page-size")
     p.add_argument("--prefill-chunk", type=int, default=0, metavar="N",
                    help="feed the prompt through in pieces of N tokens, each appended to the cache so far "
                         "(csrc/kernels/attention_extend.hip): the prefill's activation memory scales with N, not "

@@ -30,6 +30,12 @@ reads: csrc/kernels/attention_decode_fp8.hip (``kv_quantize``, ``rope_append_fp8
 rule in ``ops/reference.py::kv_quantize_ref``. The prompt's attention stays unquantized; only what is stored
 is quantized. Opt-in: without it nothing changes.
 
+``KVCache(kv_dtype="fp4")`` (``generate(kv_cache_dtype="fp4")``) keeps k / v as OCP MXFP4: e2m1 nibbles with one
+power-of-two e8m0 scale per block of 32 columns, D / 2 + D / 32 bytes per head row, about half the fp8 cache:
+csrc/kernels/attention_decode_fp4.hip (``kv_quantize_fp4``, ``rope_append_fp4``, ``attn_decode_fp4``), the rule in
+``ops/reference.py::kv_quantize_fp4_ref``. As with fp8 the prompt's attention stays unquantized. ``extend`` and the
+chunked prefill do not serve it.
+
 :class:`PagedKVCache` (``generate(kv_page_size=N)``) keeps k / v in a pool of pages of 64, 128 or 256 tokens with
 one block table per batch: a sequence pays for the pages it reserved instead of ``capacity`` rows, and a shared
 prefix is shared pages (:meth:`PagedKVCache.share_prefix`). ``prefill``, ``extend``, the chunked prefill,
@@ -59,7 +65,7 @@ from .ops import reference as ref
 SYNC_EVERY = 16  # generate(): the finished mask is read back at most once per this many tokens
 
 
-KV_DTYPES = ("model", "fp8")
+KV_DTYPES = ("model", "fp8", "fp4")
 
 
 class KVCache:
@@ -69,7 +75,11 @@ class KVCache:
     ``kv_dtype="model"`` (the default) stores k / v in ``dtype``. ``kv_dtype="fp8"`` stores every head row
     as D bytes of OCP e4m3fn (uint8 tensors ``k`` / ``v``) and one power-of-two fp32 scale (``k_scale`` /
     ``v_scale`` [B, capacity, Hkv]) by the rule of ``ops/reference.py::kv_quantize_ref``: (D + 4) / (2 D)
-    of the 16-bit cache's bytes. ``dtype`` stays the model's dtype: the dtype of q and of the output."""
+    of the 16-bit cache's bytes. ``kv_dtype="fp4"`` stores it as OCP MXFP4 by the rule of
+    ``ops/reference.py::kv_quantize_fp4_ref``: uint8 ``k`` / ``v`` [B, capacity, Hkv, D / 2] of e2m1 nibble pairs
+    and uint8 ``k_scale`` / ``v_scale`` [B, capacity, Hkv, D / 32] of e8m0 exponents, one per block of 32 columns:
+    (D / 2 + D / 32) / (2 D) of the 16-bit cache's bytes; head_dim must be a multiple of 32. ``dtype`` stays the
+    model's dtype: the dtype of q and of the output."""
 
     def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device,
                  kv_dtype: str = "model"):
@@ -81,9 +91,12 @@ class KVCache:
         if batch < 1 or capacity < 1:
             raise ValueError(f"KVCache needs batch >= 1 and capacity >= 1, got {batch}, {capacity}")
         self.batch, self.capacity, self.dtype, self.kv_dtype = batch, capacity, dtype, kv_dtype
-        self.fp8 = kv_dtype == "fp8"
-        shape = (model_args.n_layers, batch, capacity, model_args.kv_heads, model_args.head_dim)
-        self._k = torch.zeros(shape, dtype=torch.uint8 if self.fp8 else dtype, device=device)
+        self.fp8, self.fp4 = kv_dtype == "fp8", kv_dtype == "fp4"
+        D = model_args.head_dim
+        if self.fp4 and D % 32:
+            raise ValueError(f"KVCache: kv_dtype='fp4' needs head_dim a multiple of 32 (the MX block), got {D}")
+        shape = (model_args.n_layers, batch, capacity, model_args.kv_heads, D // 2 if self.fp4 else D)
+        self._k = torch.zeros(shape, dtype=torch.uint8 if self.fp8 or self.fp4 else dtype, device=device)
         self._v = torch.zeros_like(self._k)
         self.k = list(self._k.unbind(0))
         self.v = list(self._v.unbind(0))
@@ -94,11 +107,18 @@ class KVCache:
             self._v_scale = torch.ones_like(self._k_scale)
             self.k_scale = list(self._k_scale.unbind(0))
             self.v_scale = list(self._v_scale.unbind(0))
+        if self.fp4:  # an all-zero block has e = 0: byte 127
+            self._k_scale = torch.full(shape[:-1] + (D // 32,), 127, dtype=torch.uint8, device=device)
+            self._v_scale = torch.full_like(self._k_scale, 127)
+            self.k_scale = list(self._k_scale.unbind(0))
+            self.v_scale = list(self._v_scale.unbind(0))
         self.kv_len = torch.zeros(batch, dtype=torch.int32, device=device)
 
     def nbytes(self) -> int:
         n = 2 * self._k.numel() * self._k.element_size()
-        return n + 2 * self._k_scale.numel() * 4 if self.fp8 else n
+        if self.fp8 or self.fp4:
+            n += 2 * self._k_scale.numel() * self._k_scale.element_size()
+        return n
 
 
 PAGE_SIZES = (64, 128, 256)  # divide the decode chunk (256) and the extend chunk (512); multiples of the 64-key tile
@@ -125,13 +145,15 @@ class PagedKVCache:
     :meth:`share_prefix` keep it truthful (they only ever lower it); :meth:`reserve` maps pages after a row's
     mapped prefix and cannot break it."""
 
-    fp8 = False
+    fp8 = fp4 = False
     kv_dtype = "model"
     group_size = 1      # > 1 after fork(): rows g * group_size .. (g + 1) * group_size - 1 form group g
     shared_len = None   # forked: int32 [batch / group_size] on the device
 
     def __init__(self, model_args: TransformerModelArgs, batch: int, capacity: int, dtype: torch.dtype, device,
                  page_size: int = 128, n_pages: Optional[int] = None, kv_dtype: str = "model"):
+        if kv_dtype == "fp4":
+            raise ValueError("PagedKVCache: kv_dtype='fp4' is not served: a paged fp4 cache is a follow-up")
         if kv_dtype != "model":
             raise ValueError(f"PagedKVCache: kv_dtype={kv_dtype!r} is not served: a paged fp8 cache is a follow-up")
         if page_size not in PAGE_SIZES:
@@ -289,27 +311,39 @@ def _decode_hip(qkv: torch.Tensor, head_dim: int) -> bool:
     return F._note_fallback("decode attention", qkv, _ext.hip16(qkv) and head_dim in (64, 128))
 
 
+def _scale_kind(k_scale) -> Tuple[bool, bool]:
+    """(fp8, fp4) from a cache op's ``k_scale``: fp32 scales mark an fp8 cache, uint8 e8m0 bytes an fp4 cache."""
+    fp4 = k_scale is not None and k_scale.dtype == torch.uint8
+    return k_scale is not None and not fp4, fp4
+
+
 def rope_append(qkv, tab, kv_len, k_cache, v_cache, k_scale=None, v_scale=None, block_table=None, cap=None) -> None:
     """The new tokens' fused QKV rows [B * T, (Hq + 2 Hkv) D], T per sequence (B is the caches'): row
     b * T + t has q rotated in place at position kv_len[b] + t, rotated k and plain v into that cache row.
     Bit-equal to ``rope_`` on the same row at that position. T = 1 clamps the row to cap - 1; with T > 1 a
     position at or beyond the capacity stores nothing (its q takes table row cap - 1).
     With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8): the same rows, for any T, are quantized on
-    the way in -- the cache is a pure function of what the 16-bit cache would hold.
+    the way in -- the cache is a pure function of what the 16-bit cache would hold. uint8 scales mark an fp4
+    cache (:class:`KVCache`): the same, by the MXFP4 rule.
     With ``block_table`` (and the logical capacity ``cap``) the caches are the pools of a :class:`PagedKVCache`: the
     same rows through the table, bit for bit; a token whose page is unmapped stores nothing."""
-    fp8 = k_scale is not None
+    fp8, fp4 = _scale_kind(k_scale)
+    D = k_cache.shape[-1] * (2 if fp4 else 1)
     if block_table is not None:
         if _decode_hip(qkv, k_cache.shape[-1]):
             _ext.require_for(qkv).rope_append_paged_(qkv, tab, kv_len, k_cache, v_cache, block_table, cap)
         else:
             ref.rope_append_paged_ref(qkv, tab, kv_len, k_cache, v_cache, block_table, cap)
-    elif _decode_hip(qkv, k_cache.shape[-1]):
+    elif _decode_hip(qkv, D):
         C = _ext.require_for(qkv)
-        if fp8:
+        if fp4:
+            C.rope_append_fp4_(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
+        elif fp8:
             C.rope_append_fp8_(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
         else:
             C.rope_append_(qkv, tab, kv_len, k_cache, v_cache)
+    elif fp4:
+        ref.rope_append_fp4_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
     elif fp8:
         ref.rope_append_fp8_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale)
     else:
@@ -321,7 +355,8 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
                      shared_len=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """q [B, Hq, D] over the caches [B, cap, Hkv, D]: sequence b attends to keys 0 .. kv_len[b] - 1.
     Returns (o [B, Hq, D] in q's dtype, lse fp32 [B, Hq] -- the opmath dtype on the torch path).
-    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8) and the keys are their dequantized rows.
+    With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8; fp4 when the scales are uint8 too) and the keys are
+    their dequantized rows.
     With ``block_table`` / ``cap`` they are the pools of a :class:`PagedKVCache`: ``attn_decode_paged``, bit-equal
     to the dense kernel on the gathered cache. With ``group_size`` > 1 and ``shared_len`` (int32
     [B / group_size] on the device; a forked cache's fields) as well, the batch is groups of ``group_size``
@@ -329,7 +364,7 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     (csrc/kernels/attention_decode_shared.hip) reads those pages once per group. The result is the ungrouped one
     up to fp32 summation order (``ops/reference.py::attention_decode_shared_ref``)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    fp8 = k_scale is not None
+    fp8, fp4 = _scale_kind(k_scale)
     if group_size != 1 and (block_table is None or shared_len is None):
         raise ValueError("attention_decode: group_size > 1 needs a paged cache (block_table, cap) and shared_len")
     if block_table is not None:
@@ -346,12 +381,16 @@ def attention_decode(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
         return o.to(q.dtype), lse
     if _decode_hip(q, q.shape[-1]):
         C = _ext.require_for(q)
-        if fp8:
+        if fp4:
+            o, lse = C.attn_decode_fp4(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+        elif fp8:
             o, lse = C.attn_decode_fp8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
         else:
             o, lse = C.attn_decode(q, k_cache, v_cache, kv_len, scale)
         return o, lse
-    if fp8:
+    if fp4:
+        o, lse = ref.attention_decode_fp4_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+    elif fp8:
         o, lse = ref.attention_decode_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
     else:
         o, lse = ref.attention_decode_ref(q, k_cache, v_cache, kv_len, scale)
@@ -417,10 +456,12 @@ def _store_prompt_kv(k, v, kc, vc, ks, vs, block_table=None, cap=None) -> None:
         kc[:, :S].copy_(k)  # strided copies
         vc[:, :S].copy_(v)
     elif _decode_hip(k, k.shape[-1]):
-        _ext.require_for(k).kv_quantize_(k, v, kc, vc, ks, vs)
+        C = _ext.require_for(k)
+        (C.kv_quantize_fp4_ if ks.dtype == torch.uint8 else C.kv_quantize_)(k, v, kc, vc, ks, vs)
     else:
-        kc[:, :S], ks[:, :S] = ref.kv_quantize_ref(k)
-        vc[:, :S], vs[:, :S] = ref.kv_quantize_ref(v)
+        quantize = ref.kv_quantize_fp4_ref if ks.dtype == torch.uint8 else ref.kv_quantize_ref
+        kc[:, :S], ks[:, :S] = quantize(k)
+        vc[:, :S], vs[:, :S] = quantize(v)
 
 
 # ---------------------------------------------------------------------------------------
@@ -477,19 +518,28 @@ def _check_cache(model, cache, B: int):
     a = model.model_args
     if isinstance(cache, PagedKVCache) and tuple(cache.block_table.shape) != (cache.batch, cache.pages_per_seq):
         raise ValueError("PagedKVCache: the block table must be [batch, ceil(capacity / page_size)]")
-    if cache.batch != B or len(cache.k) != a.n_layers or tuple(cache.k[0].shape[2:]) != (a.kv_heads, a.head_dim):
+    fp4 = getattr(cache, "fp4", False)
+    row = a.head_dim // 2 if fp4 else a.head_dim
+    if cache.batch != B or len(cache.k) != a.n_layers or tuple(cache.k[0].shape[2:]) != (a.kv_heads, row):
         raise ValueError("KVCache does not match the model / batch")
     w = model.tok_embeddings.weight
-    kind = getattr(cache, "fp8", False)
+    kind = getattr(cache, "fp8", False) or fp4
     dtype = cache.dtype if kind else cache.k[0].dtype
     if dtype != w.dtype or cache.k[0].device != w.device:
         raise ValueError(f"KVCache is {dtype} on {cache.k[0].device}, the model {w.dtype} on {w.device}")
-    if kind and (cache.k[0].dtype != torch.uint8 or cache.k_scale[0] is None or
+    if fp4 and (cache.k[0].dtype != torch.uint8 or cache.k_scale[0] is None or cache.k_scale[0].dtype != torch.uint8 or
+                tuple(cache.k_scale[0].shape) != tuple(cache.k[0].shape[:-1]) + (a.head_dim // 32,)):
+        raise ValueError("KVCache: an fp4 cache holds uint8 k / v [B, capacity, Hkv, D / 2] and uint8 scales "
+                         "[B, capacity, Hkv, D / 32]")
+    if kind and not fp4 and (cache.k[0].dtype != torch.uint8 or cache.k_scale[0] is None or
                  tuple(cache.k_scale[0].shape) != tuple(cache.k[0].shape[:-1])):
         raise ValueError("KVCache: an fp8 cache holds uint8 k / v and fp32 scales [B, capacity, Hkv]")
 
 
 def _refuse_fp8(cache: KVCache, what: str, fp8_extend: bool = False) -> None:
+    if getattr(cache, "fp4", False):
+        raise ValueError(f"{what} does not serve an fp4 KV cache, with or without fp8_extend: there is no fp4 extend "
+                         f"kernel. Use the one-shot prefill and decode_step, or an fp8 cache with fp8_extend=True")
     if getattr(cache, "fp8", False) and not fp8_extend:
         raise ValueError(f"{what} does not serve an fp8 KV cache: the prompt's attention is defined as unquantized "
                          f"(prefill), and new tokens attending to their own dequantized keys would change that. "
@@ -547,6 +597,7 @@ def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, ret
     cache first, then query t attends to the dequantized cache rows 0 .. min(kv_len[b] + t, cap - 1), its own
     row and the other new rows included. So ``extend`` with T = 1 is ``decode_step``, and with T tokens it
     equals T ``decode_step`` calls in exact arithmetic. The flag is ignored for a cache in the model's dtype.
+    An fp4 cache is refused with ``ValueError`` whatever the flag says.
 
     On a forked :class:`PagedKVCache` ``extend`` and the chunked prefill keep using ``attn_extend_paged`` per
     sequence: only ``decode_step`` reads a group's shared pages once."""
@@ -605,7 +656,8 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     result is the one-shot prefill's up to summation order. It refuses an fp8 cache (``ValueError``): a
     piece would attend to dequantized keys. ``fp8_extend=True`` opts into exactly that (see :func:`extend`):
     every piece attends to dequantized rows, so the result differs from the one-shot prefill by quantization
-    error, not only by summation order. ``chunk = 0`` is the one-shot path, with or without the flag."""
+    error, not only by summation order. ``chunk = 0`` is the one-shot path, with or without the flag. An fp4
+    cache takes the one-shot path only: ``chunk > 0`` refuses it whatever the flag says."""
     B, S = tokens.shape
     _check_cache(model, cache, B)
     if S > cache.capacity:
@@ -856,6 +908,10 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     ``"model"`` cache gives; later tokens attend to dequantized keys and values. It needs the cache:
     ``use_cache=False`` raises ``ValueError``.
 
+    ``kv_cache_dtype="fp4"`` keeps it as OCP MXFP4 (e2m1 nibbles, one power-of-two scale per 32 columns): about
+    half of the fp8 cache again, under the same rules (the first generated token is the ``"model"`` cache's). It
+    does not combine with ``prefill_chunk`` or ``kv_page_size``.
+
     ``prefill_chunk=N`` (N > 0) feeds the prompt through :func:`prefill` in pieces of N columns, bounding the
     prefill's activation memory by B * N rows; the tokens are those of the one-shot prefill up to summation
     order. It needs the cache and refuses ``kv_cache_dtype="fp8"`` unless ``fp8_extend=True``: then every piece
@@ -891,6 +947,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
         raise ValueError(f"generate: kv_cache_dtype={kv_cache_dtype!r} needs the KV cache (use_cache=True)")
     if kv_page_size != 0 and kv_page_size not in PAGE_SIZES:
         raise ValueError(f"generate: kv_page_size must be 0 (the dense cache) or one of {PAGE_SIZES}, got {kv_page_size}")
+    if kv_page_size and use_cache and kv_cache_dtype == "fp4":
+        raise ValueError("generate: kv_page_size needs kv_cache_dtype='model': a paged fp4 cache is a follow-up")
     if kv_page_size and (not use_cache or kv_cache_dtype != "model"):
         raise ValueError("generate: kv_page_size needs the KV cache (use_cache=True) in the model's dtype "
                          "(kv_cache_dtype='model'): a paged fp8 cache is a follow-up")

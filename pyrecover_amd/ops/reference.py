@@ -406,6 +406,63 @@ def attention_extend_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scal
 
 
 # ---------------------------------------------------------------------------------------
+# MXFP4 KV cache (HIP: csrc/kernels/attention_decode_fp4.hip). A cache row, the D values of one (sequence,
+# position, kv head), is D / 32 blocks of 32 columns: D / 2 bytes of e2m1 nibble pairs (element 2i in the low
+# nibble of byte i) and D / 32 e8m0 scale bytes (e + 127), all held as uint8.
+FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitude of code 0 .. 7
+
+
+def kv_quantize_fp4_ref(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., D] (D a multiple of 32) -> (nibble pairs uint8 [..., D / 2], scale bytes uint8 [..., D / 32]) by
+    the cache's rule, on x cast to fp32 (exact for bf16 / fp16). Per block of 32 columns: amax = max |x_i|;
+    amax == 0 gives e = 0 and nibbles 0 (also for -0.0); otherwise (m, k) = frexp(amax) and
+    e = clamp(k - 3 + (m > 0.75), -127, 127), the smallest e with amax * 2^-e <= 6, so nothing saturates.
+    nibble_i = sign(x_i) << 3 | code, the code counted with comparisons against the boundaries between
+    neighbouring magnitudes (a tie goes to the even code), on |x_i| * 2^-e formed exactly in fp64: no float cast
+    rounds anything."""
+    D = x.shape[-1]
+    xf = x.float().reshape(*x.shape[:-1], D // 32, 32)
+    amax = xf.abs().amax(dim=-1)
+    m, k = torch.frexp(amax)
+    e = (k.to(torch.int32) - 3 + (m > 0.75).to(torch.int32)).clamp(-127, 127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    y = torch.ldexp(xf.abs().double(), -e.unsqueeze(-1))
+    code = ((y > 0.25).to(torch.uint8) + (y >= 0.75).to(torch.uint8) + (y > 1.25).to(torch.uint8) +
+            (y >= 1.75).to(torch.uint8) + (y > 2.5).to(torch.uint8) + (y >= 3.5).to(torch.uint8) +
+            (y > 5.0).to(torch.uint8))
+    nib = (torch.signbit(xf).to(torch.uint8) << 3 | code).masked_fill((amax == 0).unsqueeze(-1), 0)
+    nib = nib.reshape(*x.shape[:-1], D // 2, 2)
+    return nib[..., 0] | nib[..., 1] << 4, (e + 127).to(torch.uint8)
+
+
+def kv_dequantize_fp4_ref(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """nibble pairs [..., D / 2], scale bytes [..., D / 32] -> value(nibble) * 2^(byte - 127) [..., D] in ``dtype``:
+    exact in fp32 (formed in fp64)."""
+    D = 2 * q.shape[-1]
+    nib = torch.stack([q & 15, q >> 4], dim=-1).reshape(*q.shape[:-1], D // 32, 32).long()
+    val = torch.tensor(FP4_VALUES, dtype=torch.float64, device=q.device)[nib & 7]
+    val = torch.where(nib >= 8, -val, val)
+    return torch.ldexp(val, (scale.to(torch.int32) - 127).unsqueeze(-1)).reshape(*q.shape[:-1], D).to(dtype)
+
+
+def rope_append_fp4_ref(qkv, tab, kv_len, k_cache, v_cache, k_scale, v_scale) -> None:
+    """:func:`rope_append_fp8_ref` over an fp4 cache: same rows, same overflow rule, q rotated in place as there;
+    the k row is rotated in opmath, rounded once to qkv's dtype and then quantized, the v row quantized from its
+    values."""
+    B, cap, Hkv = k_cache.shape[:3]
+    bi, pos, k, v = _rope_new_rows(qkv, tab, kv_len, B, cap, Hkv, 2 * k_cache.shape[3])
+    k_cache[bi, pos], k_scale[bi, pos] = kv_quantize_fp4_ref(k)
+    v_cache[bi, pos], v_scale[bi, pos] = kv_quantize_fp4_ref(v)
+
+
+def attention_decode_fp4_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale: Optional[float] = None):
+    """:func:`attention_decode_ref` on the dequantized cache, in q's precision promoted to at least fp32."""
+    dt = up(q).dtype
+    return attention_decode_ref(q, kv_dequantize_fp4_ref(k_cache, k_scale, dt),
+                                kv_dequantize_fp4_ref(v_cache, v_scale, dt), kv_len, scale)
+
+
+# ---------------------------------------------------------------------------------------
 # Sampling (pyrecover_amd/inference.py; HIP: csrc/kernels/sample.hip)
 SAMPLE_STREAM = 3  # Philox counter word 3: after the stochastic-rounding streams 0, 1, 2 (optim/sr.py)
 

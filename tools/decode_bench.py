@@ -24,9 +24,11 @@ a cache that held ``--extend-base`` keys before (default ctx - T). ``--prefill S
 prompt once per ``--prefill-chunk`` value and prints the peak activation memory of each. ``--batch`` / ``--ctx``
 override the shapes' batch and context.
 
-``--kv-cache-dtype model|fp8|both`` picks the cache of every table: ``fp8`` is the e4m3fn cache with one
+``--kv-cache-dtype model|fp8|both|fp4|all`` picks the cache of every table: ``fp8`` is the e4m3fn cache with one
 power-of-two scale per (token, kv head) (``attn_decode_fp8``; its K/V rate counts the bytes it reads, scales
-included), ``both`` measures the two arms in one process on the same q and the same K / V values.
+included), ``both`` measures the two arms in one process on the same q and the same K / V values. ``fp4`` is the
+MXFP4 cache (``attn_decode_fp4``; e2m1 nibbles and one scale byte per 32 columns), timed beside the 16-bit call,
+``all`` the three arms, alternating over three rounds.
 
 ``--sampler torch|philox|both`` times whole generated tokens (sampling, the bookkeeping of ``generate`` and the
 decode step) per arm: ``torch`` is generate()'s default loop (``sample_token`` with a ``torch.Generator`` and
@@ -78,7 +80,8 @@ def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
     per_layer = 2 * B * ctx * Hkv * D * 2  # bytes of K and V one call reads
     per_layer8 = 2 * B * ctx * Hkv * (D + 4)  # ... from an fp8 cache: bytes and scales
     # rotate over >= 2 x the Infinity Cache (of the smaller arm's bytes)
-    n_buf = max(2, -(-2 * L3_BYTES // (per_layer8 if "fp8" in kinds else per_layer)))
+    smallest = per_layer * (D // 2 + D // 32) // (2 * D) if "fp4" in kinds else per_layer8 if "fp8" in kinds else per_layer
+    n_buf = max(2, -(-2 * L3_BYTES // smallest))
     ks = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
     vs = [torch.randn(B, ctx, Hkv, D, device=dev).bfloat16() for _ in range(n_buf)]
     q = torch.randn(B, Hq, D, device=dev).bfloat16()
@@ -115,7 +118,42 @@ def bench_attention(name, cfg, B, ctx, iters, dev, kinds=("model",)):
         print(f"  HIP fp8 {hip8:7.1f} us  {per_layer8 / hip8 / 1e6:6.2f} TB/s of {per_layer8 / 2**20:.0f} MiB (bytes and scales; "
               f"KC={C.attn_decode_fp8_chunk()}): {hip / hip8:.2f}x of the 16-bit call; "
               f"max |o - o_ref(dequantized)| {err8:.2e}")
+    if "fp4" in kinds:
+        bench_attention_fp4(C, q, ks, vs, c8 if hip8 is not None else None, n, scale, iters, per_layer, per_layer8)
     return hip, tor
+
+
+def bench_attention_fp4(C, q, ks, vs, c8, n, scale, iters, per_layer, per_layer8):
+    """``attn_decode_fp4`` over the same K / V values, quantized to MXFP4, beside the 16-bit call (and the fp8 call
+    when it was set up): the arms alternate over three rounds, every round's time is printed, the medians are
+    compared. Its K/V rate counts nibbles and scale bytes."""
+    B, ctx, Hkv, D = ks[0].shape
+    per_layer4 = 2 * B * ctx * Hkv * (D // 2 + D // 32)
+    c4 = []
+    for k, v in zip(ks, vs):
+        kq, vq = (torch.empty(B, ctx, Hkv, D // 2, dtype=torch.uint8, device=q.device) for _ in range(2))
+        sk, sv = (torch.empty(B, ctx, Hkv, D // 32, dtype=torch.uint8, device=q.device) for _ in range(2))
+        C.kv_quantize_fp4_(k, v, kq, vq, sk, sv)
+        c4.append((kq, vq, sk, sv))
+    nb = len(ks)
+    arms = [("16-bit", per_layer, lambda i: C.attn_decode(q, ks[i % nb], vs[i % nb], n, scale))]
+    if c8 is not None:
+        arms.append(("fp8", per_layer8, lambda i: C.attn_decode_fp8(q, *c8[i % nb], n, scale)))
+    arms.append(("fp4", per_layer4, lambda i: C.attn_decode_fp4(q, *c4[i % nb], n, scale)))
+    times = {a: [] for a, _, _ in arms}
+    for _ in range(3):
+        for a, _, fn in arms:
+            times[a].append(timed_us(fn, iters))
+    o4, _ = C.attn_decode_fp4(q, *c4[0], n, scale)
+    kd, vd = (ref.kv_dequantize_fp4_ref(c4[0][j], c4[0][j + 2]) for j in (0, 1))
+    err4 = (o4.float() - ref.attention_decode_ref(q, kd, vd, n, scale)[0]).abs().max().item()
+    print(f"  fp4 beside the others, KC={C.attn_decode_fp4_chunk()}, us (three rounds, median); "
+          f"max |o - o_ref(dequantized)| {err4:.2e}")
+    med16 = sorted(times["16-bit"])[1]
+    for a, nbytes, _ in arms:
+        med = sorted(times[a])[1]
+        print(f"  {a:7s} {med:8.1f} ({' '.join(f'{x:.1f}' for x in times[a])})  {nbytes / med / 1e6:5.2f} TB/s of "
+              f"{nbytes / 2**20:.0f} MiB  {med16 / med:.2f}x of the 16-bit call")
 
 
 def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model",)):
@@ -319,12 +357,13 @@ def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="mode
 
 
 def filled_cache(cfg, B, ctx, dev, kv_dtype):
-    """A full cache of standard normal K / V (quantized from them when fp8)."""
+    """A full cache of standard normal K / V (quantized from them when fp8 or fp4)."""
     cache = inf.KVCache(cfg, B, ctx, torch.bfloat16, dev, kv_dtype=kv_dtype)
     for i, (k, v) in enumerate(zip(cache.k, cache.v)):
-        if cache.fp8:
+        if cache.fp8 or cache.fp4:
             src = torch.randn(2, B, ctx, cfg.kv_heads, cfg.head_dim, device=dev).bfloat16()
-            _ext.native().kv_quantize_(src[0], src[1], k, v, cache.k_scale[i], cache.v_scale[i])
+            C = _ext.native()
+            (C.kv_quantize_fp4_ if cache.fp4 else C.kv_quantize_)(src[0], src[1], k, v, cache.k_scale[i], cache.v_scale[i])
         else:
             k.normal_()
             v.normal_()
@@ -450,8 +489,10 @@ def main():
                     help="time whole generated tokens with this sampler instead of the kernel / step tables")
     ap.add_argument("--graph", action="store_true", help="add the hipGraph-replayed philox arm (DecodeGraph)")
     ap.add_argument("--sample-bench", action="store_true", help="time the sampler alone")
-    ap.add_argument("--kv-cache-dtype", choices=("model", "fp8", "both"), default="model",
-                    help="the cache of every table: the model's dtype, fp8 (e4m3fn bytes + scales), or both arms")
+    ap.add_argument("--kv-cache-dtype", choices=("model", "fp8", "both", "fp4", "all"), default="model",
+                    help="the cache of every table: the model's dtype, fp8 (e4m3fn bytes + scales), both of them, fp4 "
+                         "(MXFP4 nibbles + block scales; the kernel table times it beside the 16-bit call), or all "
+                         "three arms. fp4 has no extend or paged kernel: --extend, --prefill, --page-size and --shared refuse it")
     ap.add_argument("--extend", type=int, default=0, metavar="T",
                     help="time attn_extend alone: T new queries per sequence appended to each shape's cache")
     ap.add_argument("--extend-base", type=int, default=None, metavar="N",
@@ -471,7 +512,10 @@ def main():
     ap.add_argument("--ctx", type=int, default=0, help="override the context (cache capacity) of every chosen shape")
     a = ap.parse_args()
     shapes = [(s[0], s[1], a.batch or s[2], a.ctx or s[3]) for s in SHAPES if s[0] in a.shapes.split(",")]
-    kinds = ("model", "fp8") if a.kv_cache_dtype == "both" else (a.kv_cache_dtype,)
+    kinds = {"both": ("model", "fp8"), "all": ("model", "fp8", "fp4")}.get(a.kv_cache_dtype, (a.kv_cache_dtype,))
+    if "fp4" in kinds and (a.extend or a.prefill or a.page_size or a.shared):
+        raise SystemExit("--kv-cache-dtype fp4 / all: there is no fp4 extend or paged kernel, so --extend, --prefill, "
+                         "--page-size and --shared take model, fp8 or both")
     dev = torch.device("cuda", 0)
     _ext.native()
     if a.sample_bench:
@@ -505,7 +549,8 @@ def main():
                 bench_tokens(name, preset, B, ctx, a.layers, a.iters, dev, samplers, a.graph, kind)
         return
     for name, preset, B, ctx in shapes:
-        bench_attention(name, get_preset(preset), B, ctx, a.iters, dev, kinds)
+        bench_attention(name, get_preset(preset), B, ctx, a.iters, dev,
+                        kinds if "fp4" not in kinds else tuple(dict.fromkeys(("model",) + kinds)))
     if not a.skip_step:
         for name, preset, B, ctx in shapes:
             for kind in kinds:
