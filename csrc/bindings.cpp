@@ -1350,6 +1350,45 @@ std::vector<at::Tensor> attn_decode_fp4(const at::Tensor& q, const at::Tensor& k
   return {o, lse};
 }
 
+// attn_extend over an MXFP4 cache (csrc/kernels/attention_extend_fp4.hip): the caches hold the T new tokens'
+// quantized rows already, and query t attends to the dequantized rows 0 .. min(kv_len[b] + t, cap - 1).
+// -> (o [B, T, Hq, D] in q's dtype, lse fp32 [B, T, Hq]). split and the workspace as attn_extend.
+std::vector<at::Tensor> attn_extend_fp4(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& kv_len,
+                                        double scale, int64_t split) {
+  const Range range_("pyrecover::attn_extend_fp4");
+  check_dev(q, "q");
+  TORCH_CHECK(split >= -1 && split <= 1, "attn_extend_fp4: split must be -1 (by shape), 0 or 1, got ", split);
+  TORCH_CHECK(q.dim() == 4 && q.size(1) > 0, "attn_extend_fp4: q must be [B, T, Hq, D], got ", q.sizes());
+  const int64_t B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+  const int64_t Dc = check_decode_fp4_common(q, k_cache, v_cache, k_scale, v_scale, &kv_len, B, "attn_extend_fp4");
+  const int64_t cap = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(Dc == D && k_cache.size(3) == D / 2, "attn_extend_fp4: q and the caches disagree on head_dim");
+  TORCH_CHECK(Hq > 0 && Hq <= 65535 && Hq % Hkv == 0, "attn_extend_fp4: n_heads must be a multiple of n_kv_heads");
+  TORCH_CHECK(T * (Hq / Hkv) <= (int64_t)INT32_MAX / 2, "attn_extend_fp4: bad shape");
+  // rows of one token contiguous, tokens at one stride across the batch: else a packed copy
+  int64_t ldq = T > 1 ? q.stride(1) : B > 1 ? q.stride(0) : Hq * D;
+  const bool view_ok = q.stride(3) == 1 && q.stride(2) == D && ldq % 8 == 0 && ldq >= Hq * D &&
+                       (B == 1 || q.stride(0) == T * ldq);
+  at::Tensor qc = view_ok ? q : q.contiguous();
+  if (!view_ok) ldq = Hq * D;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qc.data_ptr()) % 16 == 0, "attn_extend_fp4: q must be 16-B aligned");
+  const c10::DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, T, Hq, D}, q.options());
+  at::Tensor lse = at::empty({B, T, Hq}, q.options().dtype(at::kFloat));
+  pra_attn_extend_plan_t pl;
+  pra_attn_extend_plan((int)B, (int)T, (int)Hq, (int)Hkv, (int)D, (int)cap, (int)split, &pl);
+  at::Tensor ws;
+  if (pl.split) ws = at::empty({pl.ws_floats}, q.options().dtype(at::kFloat));
+  check(pra_attn_extend_fp4(dt(q), qc.data_ptr(), ldq, k_cache.data_ptr(), v_cache.data_ptr(),
+                            k_scale.data_ptr<uint8_t>(), v_scale.data_ptr<uint8_t>(), Hkv * (D / 32),
+                            kv_len.data_ptr<int>(), o.data_ptr(), lse.data_ptr<float>(),
+                            pl.split ? ws.data_ptr<float>() : nullptr, (int)B, (int)T, (int)Hq, (int)Hkv, (int)D,
+                            (int)cap, (float)scale, (int)split, stream_of(q)),
+        "attn_extend_fp4");
+  return {o, lse};
+}
+
 // Paged KV cache (csrc/kernels/attention_paged.hip): the checks of check_decode_common with pools
 // [n_pages, page, Hkv, D] (page 64 / 128 / 256), the logical capacity `cap` and the block table int32
 // [B, ceil(cap / page)] on the reference tensor's device. kv_len: absent for the prompt store.
@@ -1780,6 +1819,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"));
   m.def("attn_decode_fp4_chunk", []() { return pra_attn_decode_fp4_chunk(); });
   m.def("attn_extend_fp8", &attn_extend_fp8, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+        py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"), py::arg("split") = -1);
+  m.def("attn_extend_fp4", &attn_extend_fp4, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("kv_len"), py::arg("scale"), py::arg("split") = -1);
   m.def("rope_append_paged_", &rope_append_paged_, py::arg("qkv"), py::arg("tab"), py::arg("kv_len"), py::arg("k_pool"),
         py::arg("v_pool"), py::arg("block_table"), py::arg("cap"));

@@ -273,6 +273,12 @@ int pra_attn_decode_fp8_chunk();
 // of e2m1 nibble pairs, k_scale, v_scale uint8 [B][cap][Hkv][D / 32] of e8m0 exponents, one per block of 32
 // columns. dtype is the 16-bit type of qkv / q / o, D 64 or 128. The three are pra_kv_quantize /
 // pra_rope_append_fp8 / pra_attn_decode_fp8 over this cache: same arguments, rows, overflow rule and workspace.
+// pra_attn_extend_fp4 (attention_extend_fp4.hip) is pra_attn_extend_fp8 over it: same plan, workspace and
+// combine; ld_scale is the scale bytes between two cache rows (Hkv * D / 32 for the contiguous cache).
+hipError_t pra_attn_extend_fp4(int dtype, const void* q, long ldq, const void* k_cache, const void* v_cache,
+                               const uint8_t* k_scale, const uint8_t* v_scale, long ld_scale, const int* kv_len,
+                               void* o, float* lse, float* ws, int B, int T, int Hq, int Hkv, int D, int cap,
+                               float scale, int split, hipStream_t s);
 hipError_t pra_kv_quantize_fp4(int dtype, const void* k, const void* v, long ld, void* k_cache, void* v_cache,
                                void* k_scale, void* v_scale, int B, int S, int Hkv, int D, int cap, hipStream_t s);
 hipError_t pra_rope_append_fp4(int dtype, void* qkv, const void* tab, const int* kv_len, void* k_cache, void* v_cache,

@@ -64,6 +64,8 @@ EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllv
                "attention_extend.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
                "attention_extend_fp8.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
                                             "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+               "attention_extend_fp4.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
+                                            "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "attention_paged.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
                                        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                "attention_decode_shared.hip": ["-fno-honor-nans", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",

@@ -78,17 +78,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "attention stays unquantized, so the first generated token does not change. fp4: OCP "
                         "MXFP4, e2m1 nibbles with one power-of-two scale per 32 columns "
                         "(csrc/kernels/attention_decode_fp4.hip), about half the fp8 cache, under the same rule; "
-                        "not with --prefill-chunk or --kv-page-size")
+                        "not with --kv-page-size, and with --prefill-chunk only under --fp4-extend")
     p.add_argument("--prefill-chunk", type=int, default=0, metavar="N",
                    help="feed the prompt through in pieces of N tokens, each appended to the cache so far "
                         "(csrc/kernels/attention_extend.hip): the prefill's activation memory scales with N, not "
                         "with the prompt. 0 (default): one pass over the whole prompt. With --kv-cache-dtype fp8 "
-                        "it needs --fp8-extend")
+                        "it needs --fp8-extend, with fp4 --fp4-extend")
     p.add_argument("--fp8-extend", action="store_true",
                    help="let --prefill-chunk run on an fp8 cache (csrc/kernels/attention_extend_fp8.hip): each "
                         "piece is quantized into the cache first and attends to dequantized rows, as a decode step "
                         "does, so the tokens differ from the one-shot prefill's by quantization error. Ignored "
                         "for --kv-cache-dtype model")
+    p.add_argument("--fp4-extend", action="store_true",
+                   help="the same for an fp4 cache (csrc/kernels/attention_extend_fp4.hip): each piece of "
+                        "--prefill-chunk is quantized into the MXFP4 cache first and attends to dequantized rows. "
+                        "Ignored for any other --kv-cache-dtype")
     p.add_argument("--kv-page-size", type=int, default=0, choices=(0,) + PAGE_SIZES, metavar="N",
                    help="keep the KV cache in pages of N tokens (64, 128 or 256; csrc/kernels/attention_paged.hip): "
                         "every sequence gets the pages its own prompt and --max-new-tokens need, not the longest "
@@ -134,7 +138,7 @@ def main(argv=None) -> int:
                                stats=stats, sampler=args.sampler, graph=args.decode_graph,
                                kv_cache_dtype=args.kv_cache_dtype, prefill_chunk=args.prefill_chunk,
                                fp8_extend=args.fp8_extend, kv_page_size=args.kv_page_size,
-                               n_samples=args.n_samples)
+                               n_samples=args.n_samples, fp4_extend=args.fp4_extend)
     records = []
     for p, ids, why in zip([p for p in prompts for _ in range(args.n_samples)], tokens, reasons):
         text = tokenizer.decode(ids) if tokenizer is not None else None

@@ -34,7 +34,9 @@ is quantized. Opt-in: without it nothing changes.
 power-of-two e8m0 scale per block of 32 columns, D / 2 + D / 32 bytes per head row, about half the fp8 cache:
 csrc/kernels/attention_decode_fp4.hip (``kv_quantize_fp4``, ``rope_append_fp4``, ``attn_decode_fp4``), the rule in
 ``ops/reference.py::kv_quantize_fp4_ref``. As with fp8 the prompt's attention stays unquantized. ``extend`` and the
-chunked prefill do not serve it.
+chunked prefill refuse it unless ``fp4_extend=True``, which serves it as ``fp8_extend=True`` serves an fp8 cache: the
+T-token ``rope_append_fp4``, then ``attn_extend_fp4`` (csrc/kernels/attention_extend_fp4.hip) over the dequantized
+rows.
 
 :class:`PagedKVCache` (``generate(kv_page_size=N)``) keeps k / v in a pool of pages of 64, 128 or 256 tokens with
 one block table per batch: a sequence pays for the pages it reserved instead of ``capacity`` rows, and a shared
@@ -415,13 +417,15 @@ def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
     With ``k_scale`` / ``v_scale`` the caches are fp8 (uint8, the new rows quantized by :func:`rope_append`) and
     the keys are their dequantized rows, a query's own row and the other new rows included:
     csrc/kernels/attention_extend_fp8.hip, which converts the bytes once while staging them and is the 16-bit
-    kernel from there on. Same ``split``, same plan, same contract.
+    kernel from there on. Same ``split``, same plan, same contract. uint8 scales mark an fp4 cache (caches
+    [B, cap, Hkv, D / 2], scales [B, cap, Hkv, D / 32]): csrc/kernels/attention_extend_fp4.hip, the same with the
+    nibbles converted at staging.
 
     With ``block_table`` / ``cap`` the caches are the pools of a :class:`PagedKVCache`: ``attn_extend_paged``, both
     arms, the same plan (it does not depend on paging), bit-equal to the dense kernel at the same ``split`` on the
     gathered cache."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    fp8 = k_scale is not None
+    fp8, fp4 = _scale_kind(k_scale)
     if block_table is not None:
         if _decode_hip(q, q.shape[-1]):
             sp = -1 if split is None else int(bool(split))
@@ -431,12 +435,16 @@ def attention_extend(q, k_cache, v_cache, kv_len, scale: Optional[float] = None,
         return o.to(q.dtype), lse
     if _decode_hip(q, q.shape[-1]):
         C, sp = _ext.require_for(q), -1 if split is None else int(bool(split))
-        if fp8:
+        if fp4:
+            o, lse = C.attn_extend_fp4(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, sp)
+        elif fp8:
             o, lse = C.attn_extend_fp8(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale, sp)
         else:
             o, lse = C.attn_extend(q, k_cache, v_cache, kv_len, scale, sp)
         return o, lse
-    if fp8:
+    if fp4:
+        o, lse = ref.attention_extend_fp4_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
+    elif fp8:
         o, lse = ref.attention_extend_fp8_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale)
     else:
         o, lse = ref.attention_extend_ref(q, k_cache, v_cache, kv_len, scale)
@@ -536,10 +544,12 @@ def _check_cache(model, cache, B: int):
         raise ValueError("KVCache: an fp8 cache holds uint8 k / v and fp32 scales [B, capacity, Hkv]")
 
 
-def _refuse_fp8(cache: KVCache, what: str, fp8_extend: bool = False) -> None:
-    if getattr(cache, "fp4", False):
-        raise ValueError(f"{what} does not serve an fp4 KV cache, with or without fp8_extend: there is no fp4 extend "
-                         f"kernel. Use the one-shot prefill and decode_step, or an fp8 cache with fp8_extend=True")
+def _refuse_fp8(cache: KVCache, what: str, fp8_extend: bool = False, fp4_extend: bool = False) -> None:
+    if getattr(cache, "fp4", False) and not fp4_extend:
+        raise ValueError(f"{what} does not serve an fp4 KV cache, with or without fp8_extend: the prompt's attention "
+                         f"is defined as unquantized (prefill). Opt in with fp4_extend=True (generate.py --fp4-extend): "
+                         f"the new tokens are quantized into the cache first and every query attends to dequantized "
+                         f"rows, as in decode_step")
     if getattr(cache, "fp8", False) and not fp8_extend:
         raise ValueError(f"{what} does not serve an fp8 KV cache: the prompt's attention is defined as unquantized "
                          f"(prefill), and new tokens attending to their own dequantized keys would change that. "
@@ -580,7 +590,7 @@ def _extend_layers(model, tokens: torch.Tensor, cache: KVCache):
 
 @torch.no_grad()
 def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, return_all: bool = False,
-           fp8_extend: bool = False) -> torch.Tensor:
+           fp8_extend: bool = False, fp4_extend: bool = False) -> torch.Tensor:
     """Append ``n_new[b]`` tokens (``tokens`` [B, T] right-padded, 1 <= n_new[b] <= T, values outside are
     clamped) to every sequence at its own ``kv_len[b]`` -> logits [B, V] of row n_new[b] - 1, the next
     position's; ``kv_len += n_new`` (clamped at the capacity). A follow-up turn, a continuation after a
@@ -597,7 +607,9 @@ def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, ret
     cache first, then query t attends to the dequantized cache rows 0 .. min(kv_len[b] + t, cap - 1), its own
     row and the other new rows included. So ``extend`` with T = 1 is ``decode_step``, and with T tokens it
     equals T ``decode_step`` calls in exact arithmetic. The flag is ignored for a cache in the model's dtype.
-    An fp4 cache is refused with ``ValueError`` whatever the flag says.
+    An fp4 cache is refused with ``ValueError`` whatever ``fp8_extend`` says; ``fp4_extend=True`` serves it by the
+    same rule (the T-token ``rope_append_fp4``, then ``attn_extend_fp4`` over the dequantized rows), and is ignored
+    for any other cache.
 
     On a forked :class:`PagedKVCache` ``extend`` and the chunked prefill keep using ``attn_extend_paged`` per
     sequence: only ``decode_step`` reads a group's shared pages once."""
@@ -605,7 +617,7 @@ def extend(model, tokens: torch.Tensor, n_new: torch.Tensor, cache: KVCache, ret
         raise ValueError(f"extend: tokens must be [B, T] with T >= 1, got {tuple(tokens.shape)}")
     B, T = tokens.shape
     _check_cache(model, cache, B)
-    _refuse_fp8(cache, "extend", fp8_extend)
+    _refuse_fp8(cache, "extend", fp8_extend, fp4_extend)
     n_new = n_new.to(device=tokens.device, dtype=torch.long).clamp(1, T)
     h, pending = _extend_layers(model, tokens, cache)
     cache.kv_len.copy_((cache.kv_len + n_new).clamp(max=cache.capacity))
@@ -641,7 +653,7 @@ def _prefill_chunked(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVC
 
 @torch.no_grad()
 def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chunk: int = 0,
-            fp8_extend: bool = False) -> torch.Tensor:
+            fp8_extend: bool = False, fp4_extend: bool = False) -> torch.Tensor:
     """tokens [B, S] (ragged prompts right-padded), lens [B] in 1 .. S -> logits [B, V] of row
     lens[b] - 1 of each sequence. Fills the cache rows 0 .. S - 1 and sets kv_len = lens. Causal
     attention makes every position below lens[b] independent of the padding; no [B, S, V] logits exist.
@@ -657,7 +669,8 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     piece would attend to dequantized keys. ``fp8_extend=True`` opts into exactly that (see :func:`extend`):
     every piece attends to dequantized rows, so the result differs from the one-shot prefill by quantization
     error, not only by summation order. ``chunk = 0`` is the one-shot path, with or without the flag. An fp4
-    cache takes the one-shot path only: ``chunk > 0`` refuses it whatever the flag says."""
+    cache is the same story under its own flag: ``chunk > 0`` refuses it whatever ``fp8_extend`` says and serves it
+    with ``fp4_extend=True``."""
     B, S = tokens.shape
     _check_cache(model, cache, B)
     if S > cache.capacity:
@@ -666,7 +679,7 @@ def prefill(model, tokens: torch.Tensor, lens: torch.Tensor, cache: KVCache, chu
     if chunk < 0:
         raise ValueError(f"prefill: chunk must be >= 0, got {chunk}")
     if chunk > 0:
-        _refuse_fp8(cache, "prefill(chunk > 0)", fp8_extend)
+        _refuse_fp8(cache, "prefill(chunk > 0)", fp8_extend, fp4_extend)
         return _prefill_chunked(model, tokens, lens, cache, int(chunk))
     emb = model.tok_embeddings.weight
     h = F.embedding(tokens, emb, model._slot([emb]))
@@ -882,7 +895,7 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
              top_p: float = 1.0, seed: int = 0, eos_id: Optional[int] = None, use_cache: bool = True,
              stats: Optional[Dict] = None, sampler: str = "torch", graph: bool = False,
              kv_cache_dtype: str = "model", prefill_chunk: int = 0, fp8_extend: bool = False,
-             kv_page_size: int = 0, n_samples: int = 1) -> Tuple[List[List[int]], List[str]]:
+             kv_page_size: int = 0, n_samples: int = 1, fp4_extend: bool = False) -> Tuple[List[List[int]], List[str]]:
     """Generate up to ``max_new_tokens`` tokens after each prompt (lists of token ids, ragged).
 
     Returns (generated ids per prompt, finish reason per prompt): ``eos`` (the last id is ``eos_id``),
@@ -910,13 +923,14 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
 
     ``kv_cache_dtype="fp4"`` keeps it as OCP MXFP4 (e2m1 nibbles, one power-of-two scale per 32 columns): about
     half of the fp8 cache again, under the same rules (the first generated token is the ``"model"`` cache's). It
-    does not combine with ``prefill_chunk`` or ``kv_page_size``.
+    does not combine with ``kv_page_size``, and with ``prefill_chunk`` only under ``fp4_extend=True``.
 
     ``prefill_chunk=N`` (N > 0) feeds the prompt through :func:`prefill` in pieces of N columns, bounding the
     prefill's activation memory by B * N rows; the tokens are those of the one-shot prefill up to summation
     order. It needs the cache and refuses ``kv_cache_dtype="fp8"`` unless ``fp8_extend=True``: then every piece
     attends to dequantized cache rows (:func:`extend`), and the tokens differ from the one-shot prefill's by
-    quantization error too. The flag does nothing for a ``"model"`` cache. ``stats["prefill_chunks"]`` is the
+    quantization error too. The flag does nothing for a ``"model"`` cache. ``fp4_extend=True`` is the same opt-in
+    for ``kv_cache_dtype="fp4"`` (csrc/kernels/attention_extend_fp4.hip). ``stats["prefill_chunks"]`` is the
     number of pieces (0: the one-shot prefill).
 
     ``kv_page_size=N`` (64, 128 or 256; 0, the default, is the dense cache exactly as before) keeps the cache in
@@ -995,7 +1009,8 @@ def generate(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, tempe
     elif use_cache:
         cache = KVCache(args, B, cap, dtype, device, kv_cache_dtype)
     if use_cache:
-        logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk, fp8_extend=fp8_extend)
+        logits = prefill(model, buf[:, :S], lens, cache, chunk=prefill_chunk, fp8_extend=fp8_extend,
+                         fp4_extend=fp4_extend)
     else:
         bi = torch.arange(B, device=device)
         logits = model(buf[:, :S])[bi, lens - 1]

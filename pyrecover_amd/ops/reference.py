@@ -462,6 +462,15 @@ def attention_decode_fp4_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scal
                                 kv_dequantize_fp4_ref(v_cache, v_scale, dt), kv_len, scale)
 
 
+def attention_extend_fp4_ref(q, k_cache, v_cache, k_scale, v_scale, kv_len, scale: Optional[float] = None):
+    """:func:`attention_extend_ref` on the dequantized fp4 cache, in q's precision promoted to at least fp32 (HIP:
+    csrc/kernels/attention_extend_fp4.hip). The caches hold the T new tokens' quantized rows already; whatever
+    nibbles and scale bytes lie beyond a row's bound never reach its output."""
+    dt = up(q).dtype
+    return attention_extend_ref(q, kv_dequantize_fp4_ref(k_cache, k_scale, dt),
+                                kv_dequantize_fp4_ref(v_cache, v_scale, dt), kv_len, scale)
+
+
 # ---------------------------------------------------------------------------------------
 # Sampling (pyrecover_amd/inference.py; HIP: csrc/kernels/sample.hip)
 SAMPLE_STREAM = 3  # Philox counter word 3: after the stochastic-rounding streams 0, 1, 2 (optim/sr.py)

@@ -161,8 +161,8 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model
     before the append (default ctx - T: the append fills the cache). With base 0 the call is a causal forward,
     and the document-masked forward (one document per row) is timed at the same shape beside it. ``split``:
     -1 by plan, 0 the single pass, 1 the key split. With "fp8" in ``kinds`` the same caches, quantized, are timed
-    through ``attn_extend_fp8`` in the same process (same plan, same rotation). With more than one arm (fp8,
-    docs_fwd) the arms alternate over three rounds; every round's time is printed, the median is the headline."""
+    through ``attn_extend_fp8`` in the same process (same plan, same rotation), with "fp4" through
+    ``attn_extend_fp4``. With more than one arm (fp8, fp4, docs_fwd) the arms alternate over three rounds; every round's time is printed, the median is the headline."""
     C = _ext.native()
     Hq, Hkv, D = cfg.n_heads, cfg.kv_heads, cfg.head_dim
     base = ctx - T if base is None else base
@@ -187,6 +187,14 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model
             C.kv_quantize_(k, v, kq, vq, sk, sv)
             c8.append((kq, vq, sk, sv))
         arms.append(("fp8", lambda i: C.attn_extend_fp8(q, *c8[i % n_buf], n, scale, split)))
+    c4 = []
+    if "fp4" in kinds:
+        for k, v in zip(ks, vs):
+            kq, vq = (torch.empty(B, ctx, Hkv, D // 2, dtype=torch.uint8, device=dev) for _ in range(2))
+            sk, sv = (torch.empty(B, ctx, Hkv, D // 32, dtype=torch.uint8, device=dev) for _ in range(2))
+            C.kv_quantize_fp4_(k, v, kq, vq, sk, sv)
+            c4.append((kq, vq, sk, sv))
+        arms.append(("fp4", lambda i: C.attn_extend_fp4(q, *c4[i % n_buf], n, scale, split)))
     with_docs = base == 0 and T % 128 == 0
     if with_docs:
         ds = torch.zeros(B, T, dtype=torch.int32, device=dev)
@@ -224,6 +232,16 @@ def bench_extend(name, cfg, B, ctx, T, base, iters, dev, split=-1, kinds=("model
             kd, vd = (ref.kv_dequantize_ref(c8[0][j], c8[0][j + 2]) for j in (0, 1))
             o_ref, _ = ref.attention_extend_ref(q.float(), kd, vd, n, scale)
             print(f"  max |o - o_ref(dequantized)| {(o8.float() - o_ref).abs().max().item():.2e}")
+    if c4:
+        per4, hip4 = per_layer // (2 * D) * (D // 2 + D // 32), med["fp4"]
+        print(f"  HIP fp4 {hip4:7.1f} us  {flop / hip4 / 1e6:7.1f} TFLOP/s  {per4 / hip4 / 1e6:6.2f} TB/s of "
+              f"{per4 / 2**20:.0f} MiB (nibbles and scales): {hip / hip4:.2f}x of the 16-bit call  "
+              f"(median of rounds: {every['fp4']})")
+        if T * B * ctx <= 1 << 24:
+            o4, _ = C.attn_extend_fp4(q, *c4[0], n, scale, split)
+            kd, vd = (ref.kv_dequantize_fp4_ref(c4[0][j], c4[0][j + 2]) for j in (0, 1))
+            o_ref, _ = ref.attention_extend_ref(q.float(), kd, vd, n, scale)
+            print(f"  max |o - o_ref(dequantized)| {(o4.float() - o_ref).abs().max().item():.2e}")
     if with_docs:
         docs = med["docs"]
         od, _ = C.attn_fwd(q, kk[0], vv[0], scale, True, ds)
@@ -328,7 +346,7 @@ def bench_shared(name, cfg, G, ctx, page, N, iters, dev):
 def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="model"):
     """``prefill`` of a B x S prompt, one-shot (chunk 0) and in pieces: milliseconds and the peak of
     ``torch.cuda.max_memory_allocated`` above what the model and the cache hold. An fp8 cache takes the pieces
-    with ``fp8_extend=True``."""
+    with ``fp8_extend=True``, an fp4 cache with ``fp4_extend=True``."""
     cfg = get_preset(preset, n_layers=layers, seq_len=S)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.bfloat16)
@@ -343,14 +361,15 @@ def bench_prefill(name, preset, B, S, layers, chunks, iters, dev, kv_dtype="mode
     print(f"{name}: prefill of B={B} x S={S}, {layers} layers, bf16, {kv_dtype} cache (model + cache "
           f"{torch.cuda.memory_allocated() / 2**30:.2f} GiB resident)")
     first = None
+    opt = dict(fp8_extend=True, fp4_extend=True)
     for c in chunks:
-        inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True)  # library warm-up and GEMM tuning at this piece's shapes
+        inf.prefill(model, tok, lens, cache, chunk=c, **opt)  # library warm-up and GEMM tuning at this piece's shapes
         torch.cuda.synchronize()
         resident = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
-        us = timed_us(lambda _: inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True), iters, 1)
+        us = timed_us(lambda _: inf.prefill(model, tok, lens, cache, chunk=c, **opt), iters, 1)
         peak = torch.cuda.max_memory_allocated() - resident
-        logits = inf.prefill(model, tok, lens, cache, chunk=c, fp8_extend=True).float()
+        logits = inf.prefill(model, tok, lens, cache, chunk=c, **opt).float()
         first = logits if first is None else first
         print(f"  chunk {c:5d}: prefill_ms {us / 1e3:9.2f}  peak activations {peak / 2**30:7.3f} GiB  "
               f"max |logits - logits(chunk {chunks[0]})| {(logits - first).abs().max().item():.3e}")
@@ -492,7 +511,7 @@ def main():
     ap.add_argument("--kv-cache-dtype", choices=("model", "fp8", "both", "fp4", "all"), default="model",
                     help="the cache of every table: the model's dtype, fp8 (e4m3fn bytes + scales), both of them, fp4 "
                          "(MXFP4 nibbles + block scales; the kernel table times it beside the 16-bit call), or all "
-                         "three arms. fp4 has no extend or paged kernel: --extend, --prefill, --page-size and --shared refuse it")
+                         "three arms. fp4 has no paged kernel: --page-size and --shared refuse it")
     ap.add_argument("--extend", type=int, default=0, metavar="T",
                     help="time attn_extend alone: T new queries per sequence appended to each shape's cache")
     ap.add_argument("--extend-base", type=int, default=None, metavar="N",
@@ -513,9 +532,9 @@ def main():
     a = ap.parse_args()
     shapes = [(s[0], s[1], a.batch or s[2], a.ctx or s[3]) for s in SHAPES if s[0] in a.shapes.split(",")]
     kinds = {"both": ("model", "fp8"), "all": ("model", "fp8", "fp4")}.get(a.kv_cache_dtype, (a.kv_cache_dtype,))
-    if "fp4" in kinds and (a.extend or a.prefill or a.page_size or a.shared):
-        raise SystemExit("--kv-cache-dtype fp4 / all: there is no fp4 extend or paged kernel, so --extend, --prefill, "
-                         "--page-size and --shared take model, fp8 or both")
+    if "fp4" in kinds and (a.page_size or a.shared):
+        raise SystemExit("--kv-cache-dtype fp4 / all: there is no paged fp4 kernel, so --page-size and --shared take "
+                         "model, fp8 or both")
     dev = torch.device("cuda", 0)
     _ext.native()
     if a.sample_bench:
